@@ -68,12 +68,44 @@ def parse():
                     "region with HIP events around every large launch class -> `roofline.worst_large_launch`)")
     ap.add_argument("--no-lora-record", action="store_true", help="skip the `lora_config` sub-record (N = 1 only: recipes/config_lora.yaml's adapter set "
                     "on the same model and micro-batch, three timed steps + the frozen-base forward + input-gradient reference)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed to "
+                    "DIR/*.npy: loss.npy (float32 [1]), grad_norms.npy (float64: L2 norm of every trainable parameter's gradient, parameters "
+                    "in name order) and grad_sample.npy (float32: a fixed, seeded sample of up to %d elements of each of those gradients, "
+                    "same order)" % DUMP_SAMPLE_PER_PARAM)
     ap.add_argument("--ep", action="store_true", help="BASELINE config #5 instead of #3: routed experts sharded over the N ranks (all-to-all "
                                                       "dispatch over xGMI), everything else data-parallel; not what the driver runs")
     args = ap.parse_args()
     if args.long:
         args.batch, args.seq, args.images, args.recompute = 1, 65536, 8, True
     return args
+
+
+DUMP_SAMPLE_PER_PARAM = 4096
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(model, loss, out_dir):
+    """--dump-outputs: the loss and the parameter gradients of the step just run, as float32 / float64 .npy files (see parse()).  The
+    sample indices come from a CPU generator with a fixed seed, so two builds of the project are compared element for element."""
+    import numpy as np
+
+    named = [(n, p) for n, p in sorted(model.named_parameters()) if p.requires_grad and p.grad is not None]
+    g = torch.Generator().manual_seed(0)
+    norms, samples = [], []
+    for _, p in named:
+        grad = p.grad.detach().reshape(-1)
+        idx = torch.randint(grad.numel(), (min(grad.numel(), DUMP_SAMPLE_PER_PARAM),), generator=g)
+        norms.append(torch.linalg.vector_norm(grad, dtype=torch.float64).item())
+        samples.append(grad[idx.to(grad.device)].float().cpu())
+    arrays = {"loss": np.array([float(loss)], dtype=np.float32), "grad_norms": np.array(norms, dtype=np.float64),
+              "grad_sample": torch.cat(samples).numpy().astype(np.float32) if samples else np.zeros(0, np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: --dump-outputs: {len(named)} gradients, {total} bytes -> {out_dir}", file=sys.stderr, flush=True)
 
 
 def init_params(model, seed):
@@ -777,6 +809,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, loss, args.dump_outputs)   # before the sub-records below: they run further steps
     tokens = world * B * S * args.steps
     if rank == 0:
         M = B * S * cfg.moe_topk

@@ -51,3 +51,28 @@ def test_bench_line_carries_the_contract(world):
         assert lora["roofline"]["bound"] == "mfma" and "lora_dropout" not in lora and "dropout=0.05" in lora["workload"]
     else:
         assert "long64k" not in res and "generate_config2" not in res
+
+
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss and gradient sample as float .npy files, identical for two runs with the same
+    arguments; --steps sets the number of timed steps (two fc1 launches per step at this depth)."""
+    import numpy as np
+
+    skip = "--no-long64k --no-inference-records --no-fusions-ab --no-lora-record --no-launch-classes --steps 3"
+    runs = []
+    for i in range(2):
+        out_dir = tmp_path / f"run{i}"
+        env = dict(os.environ, ARIA_DRY_EXTRA=f"{skip} --dump-outputs {out_dir}")
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_dry_run.py")], cwd=ROOT, env=env, capture_output=True,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert res["steps"] == 3 and res["roofline"]["launches_timed"] == 3 * 2 and res["ms_per_step"] > 0
+        files = {p.name: np.load(p) for p in out_dir.iterdir()}
+        assert set(files) == {"loss.npy", "grad_norms.npy", "grad_sample.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert abs(float(files["loss.npy"][0]) - res["config"]["loss"]) <= 1e-4 * max(1.0, abs(res["config"]["loss"]))
+        assert files["grad_norms.npy"].size > 0 and np.isfinite(files["grad_sample.npy"]).all() and (files["grad_norms.npy"] > 0).any()
+        runs.append(files)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name

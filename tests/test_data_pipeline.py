@@ -1,6 +1,7 @@
-"""aria_amd.data (aria/data.py:123-233: dataset directory format, dataset_mixer fractions, seed-42 shuffle) against the live reference
-where it is importable, and a short fine-tune of aria_amd.train on such a dataset (real collate path, emulator kernels)."""
+"""aria_amd.data (aria/data.py:123-233: dataset directory format, dataset_mixer fractions, seed-42 shuffle) against what the reference
+returned on the same datasets (tests/golden/reference_data.json, oracle/make_golden_reference_cases.py), and a short fine-tune of aria_amd.train on such a dataset (real collate path, emulator kernels)."""
 import json
+import os
 
 import numpy as np
 import pytest
@@ -8,7 +9,6 @@ import torch
 
 from aria_amd import data as D
 from oracle.ref_processing import StubTokenizer
-from oracle.ref_shims import reference_available
 
 
 def make_dataset(root, n, tag, with_test=False, extra=False):
@@ -55,22 +55,18 @@ def test_mixing_rule_and_layout(tmp_path):
     assert len(got) == 5 + 2 and got[0] == [1, 3] and got[5] == [1, 3]
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference checkout not present")
 def test_mix_datasets_equals_the_reference(tmp_path):
-    from oracle.ref_processing import load_reference_processing
-
-    ns = load_reference_processing()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data.json")) as f:
+        want = json.load(f)["mix_datasets"]     # the reference's rows for the same two datasets, image paths under "<root>"
     a, b = tmp_path / "a", tmp_path / "b"
     make_dataset(a, 7, "a", with_test=True), make_dataset(b, 4, "b")
-    cfg = {str(a): 0.6, str(b): 3}
-    want = ns.data.mix_datasets(cfg)
-    got = D.mix_datasets(cfg)
+    got = D.mix_datasets({str(a): 0.6, str(b): 3})
     assert len(want["train"]) == len(got["train"])
     for w, g in zip(want["train"], got["train"]):
-        assert w["images"] == g["images"] and w["video"] == g["video"]
-        assert [(m["role"], [(c["type"], c["text"]) for c in m["content"]]) for m in w["messages"]] == \
-               [(m["role"], [(c["type"], c["text"]) for c in m["content"]]) for m in g["messages"]]
-    assert len(want["test"]) == len(got["test"]) == 1
+        assert w["images"] == (None if g["images"] is None else [str(p).replace(str(tmp_path), "<root>") for p in g["images"]])
+        assert w["video"] == g["video"]
+        assert w["messages"] == [[m["role"], [[c["type"], c["text"]] for c in m["content"]]] for m in g["messages"]]
+    assert want["n_test"] == len(got["test"]) == 1
 
 
 def test_finetune_on_a_local_dataset(tmp_path):

@@ -1,10 +1,11 @@
 """Data-side callers of the hot path, CPU only, bit-exact.
 
-* AriaVisionProcessor: against tests/golden/processing.json (written by oracle/ref_processing.py from the reference's own class) and,
-  when /root/reference is present, tensor-for-tensor against the reference itself.
+* AriaVisionProcessor: against tests/golden/processing.json (written by oracle/ref_processing.py from the reference's own class) and
+  tensor-for-tensor (shape, dtype, sha256) against tests/golden/reference_data.json (oracle/make_golden_reference_cases.py).
 * AriaProcessor: the strings the reference's own tests assert (tests/test_aria_processor.py:41-187), with a stub tokenizer in place of
   the unreachable hub tokenizer.
-* apply_chat_template_and_tokenize / collate_fn: against the reference's functions on the same stub tokenizer."""
+* apply_chat_template_and_tokenize / collate_fn: against what the reference's functions returned on the same stub tokenizer
+  (tests/golden/reference_data.json)."""
 import copy
 import json
 import os
@@ -13,11 +14,23 @@ import pytest
 import torch
 
 from aria_amd import processing as P
-from oracle import ref_shims
 from oracle.ref_processing import StubTokenizer, digest, test_images as make_images
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-needs_reference = pytest.mark.skipif(not ref_shims.reference_available(), reason="/root/reference not present")
+
+
+def reference_data():
+    with open(os.path.join(HERE, "golden", "reference_data.json")) as f:
+        return json.load(f)
+
+
+def assert_same_tensors(got, want, what):
+    """``want``: {name: {shape, dtype, sha256}} of the reference's tensors (bf16 hashed through its int16 bits, as the fixture was)."""
+    assert set(got) == set(want), (what, sorted(got), sorted(want))
+    for k, w in want.items():
+        t = got[k]
+        h = digest(t.view(torch.int16) if t.dtype == torch.bfloat16 else t)
+        assert (list(t.shape), str(t.dtype), h) == (w["shape"], w["dtype"], w["sha256"]), (what, k)
 
 MESSAGES = [{"role": "user", "content": [{"text": None, "type": "image"}, {"text": "describe the image", "type": "text"}]}]
 PROMPT = "<|im_start|>user\n<fim_prefix><|img|><fim_suffix>describe the image<|im_end|>\n<|im_start|>assistant\n"
@@ -45,23 +58,16 @@ def test_vision_processor_matches_the_reference_fixture(size, split):
     assert digest(pv) == want["pixel_values_sha256"] and digest(pm) == want["pixel_mask_sha256"]
 
 
-@needs_reference
 def test_vision_processor_equals_the_reference_tensor_for_tensor():
-    from oracle.ref_processing import load_reference_processing
-
-    ref = load_reference_processing().vp.AriaVisionProcessor(max_image_size=490)
+    want = reference_data()
     mine = P.AriaVisionProcessor(max_image_size=490)
-    for kw in (dict(max_image_size=490, split_image=True), dict(max_image_size=None, min_image_size=None)):
-        a, b = ref(make_images(), **kw), mine(make_images(), **kw)
-        for k in ("pixel_values", "pixel_mask", "num_crops"):
-            assert torch.equal(a[k], b[k]), (k, kw)
-    for fn in ("_select_best_resolution",):
-        for w, h in ((768, 768), (1000, 300), (300, 1000), (10, 10), (5000, 700)):
-            assert getattr(load_reference_processing().vp, fn)(w, h, P.DEFAULT_SPLIT_RATIO, 490) == P.select_best_resolution(
-                w, h, P.DEFAULT_SPLIT_RATIO, 490)
+    for name, kw in (("490_split", dict(max_image_size=490, split_image=True)), ("unbounded", dict(max_image_size=None, min_image_size=None))):
+        b = mine(make_images(), **kw)
+        assert_same_tensors({k: b[k] for k in ("pixel_values", "pixel_mask", "num_crops")}, want["vision_processor"][name], kw)
+    for w, h, best in want["select_best_resolution"]:
+        assert list(P.select_best_resolution(w, h, P.DEFAULT_SPLIT_RATIO, 490)) == best, (w, h)
 
 
-@needs_reference
 @pytest.mark.parametrize("w,h", [(1, 1), (17, 335), (337, 336), (491, 50), (981, 600), (3000, 3)])
 def test_vision_processor_equals_the_reference_on_odd_sizes(w, h):
     """degenerate and off-by-one sizes around the 336 / 490 / 980 thresholds (a wider sweep, 461 size x mode combinations up to 3000 px,
@@ -69,15 +75,11 @@ def test_vision_processor_equals_the_reference_on_odd_sizes(w, h):
     import numpy as np
     from PIL import Image
 
-    from oracle.ref_processing import load_reference_processing
-
+    want = reference_data()["odd_sizes"]
     img = Image.fromarray(np.random.default_rng(w * 7 + h).integers(0, 255, (h, w, 3), dtype=np.uint8))
-    ref_cls = load_reference_processing().vp.AriaVisionProcessor
     for size, split in ((490, False), (490, True), (980, False)):
-        a = ref_cls(max_image_size=size)([img], max_image_size=size, split_image=split)
         b = P.AriaVisionProcessor(max_image_size=size)([img], max_image_size=size, split_image=split)
-        for k in ("pixel_values", "pixel_mask", "num_crops"):
-            assert torch.equal(a[k], b[k]), (k, size, split)
+        assert_same_tensors({k: b[k] for k in ("pixel_values", "pixel_mask", "num_crops")}, want[f"{w}x{h}_{size}_{int(split)}"], (size, split))
 
 
 def test_invalid_max_image_size_raises(processor, sample_image):
@@ -163,32 +165,19 @@ def test_label_masking_properties():
         P.apply_chat_template_and_tokenize(copy.deepcopy(CONVERSATIONS), tok, iter([torch.tensor(1)]), max_image_size=500)
 
 
-@needs_reference
 def test_chatml_and_collate_equal_the_reference():
-    from oracle.ref_processing import load_reference_processing
-
-    ns = load_reference_processing()
+    want = reference_data()
     tok = StubTokenizer()
     tok.pad_token = tok.unk_token
     for size, length in ((490, 4096), (980, 4096), (490, 300)):
-        a = ns.data.apply_chat_template_and_tokenize(copy.deepcopy(CONVERSATIONS), tok, iter([torch.tensor(3)]), max_length=length,
-                                                     max_image_size=size)
         b = P.apply_chat_template_and_tokenize(copy.deepcopy(CONVERSATIONS), tok, iter([torch.tensor(3)]), max_length=length,
                                                max_image_size=size)
-        assert set(a) == set(b) and all(torch.equal(a[k], b[k]) for k in a), (size, length)
-    # collate: same examples through the reference's image processor + its ChatML function vs the product's collate_fn
+        assert_same_tensors(b, want["chatml"][f"{size}_{length}"], (size, length))
+    # collate: the reference's image processor + its ChatML function (recorded) vs the product's collate_fn on the same examples
     imgs = make_images()[:2]
     examples = [{"images": [imgs[0]], "messages": CONVERSATIONS[0], "video": None}, {"images": None, "messages": CONVERSATIONS[1], "video": None}]
-    refp = ns.vp.AriaVisionProcessor(max_image_size=490)
-    image_inputs = refp([imgs[0]], split_image=True)
-    want = ns.data.apply_chat_template_and_tokenize(copy.deepcopy([e["messages"] for e in examples]), tok,
-                                                    iter(image_inputs.pop("num_crops")), max_length=100000, max_image_size=490)
-    want.update(image_inputs)
-    want["pixel_values"] = want["pixel_values"].to(torch.bfloat16)
     got = P.collate_fn(copy.deepcopy(examples), tok, P.AriaVisionProcessor(max_image_size=490), split_image=True, max_seq_length=100000)
-    assert set(got) == set(want)
-    for k in want:
-        assert torch.equal(got[k], want[k]), k
+    assert_same_tensors(got, want["collate"], "collate")
 
 
 def test_processor_output_feeds_the_model_end_to_end():

@@ -39,9 +39,7 @@ def test_adamw_kernel_matches_torch():
 def test_recipe_yaml_is_honoured():
     from aria_amd.train import load_config
 
-    ref = "/root/reference/recipes/config_full.yaml"
-    if not os.path.exists(ref):
-        pytest.skip("reference recipes not present")
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "recipe_config_full.yaml")   # the reference's recipes/config_full.yaml
     cfg = load_config(["--config", ref, "max_steps=3", "--learning_rate", "1e-4"])
     assert cfg["per_device_train_batch_size"] == 8 and cfg["gradient_accumulation_steps"] == 2 and cfg["max_seq_length"] == 2048
     assert cfg["freeze_vit"] is True and cfg["freeze_projector"] is False and cfg["gradient_checkpointing"] is True
