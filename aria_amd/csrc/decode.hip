@@ -21,6 +21,7 @@
 // materialises a bf16 tensor); only the fp32 summation ORDER inside a dot product differs from the MFMA kernels.
 #include "aria_device.h"
 #include "aria_hip.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
@@ -859,6 +860,290 @@ Scratch carve(char* base, int64_t L, int64_t D, int64_t H, int64_t hd, int64_t E
     return s;
 }
 
+// ---- int8 weight-only engine (aria_decode_token_w8, aria_gemv_w8, aria_dequant_w8_bf16) ----------------------------------------------
+// Weights are int8 codes q [rows, K] with one bf16 scale s per row (aria_amd/quantize.py): w = q * s.  A lane reads the 8 code bytes of
+// chunk c = l + 64 i of a row -- the SAME lane <-> chunk mapping as the bf16 engine's 16-byte chunks of 8 weights, so load_vector (and its
+// RMSNorm fold) and the down-projection's LDS activation images are the bf16 engine's, unchanged; a weight load is an 8-byte nt load.
+// Numerics: every dot product is an fp32 fma chain over exact operands (an int8 code and a bf16 activation are both exact in fp32); the
+// row scale multiplies the fp32 sum once, y = bf16(s * sum_k x_k q_k); every other rounding point is where the bf16 engine has it.
+// Conversion, per dword of 4 codes, as written: u = q ^ 0x80808080, float(u_b) - 128 (exact, -128 codes included), acc += that * x in
+// packed fp32 fmas.  What hipcc emits for gfx950 (tests/test_isa_guards_w8.py keeps the loads honest; the count is read off the ISA): per
+// dword 1 v_xor_b32, bytes 0 / 1 as a sign extend (v_add_u32_sdwa) + v_cvt_f32_i32 each, bytes 2 / 3 as v_cvt_f32_ubyte2 / 3 + one
+// v_pk_add_f32, 2 v_pk_fma_f32 -- 10 vector instructions per 4 codes, 40 per 16 weight bytes (the bf16 engine: 4 v_dot2c_f32_bf16 per
+// 16 bytes = 8 weights).  The activation chunk is unpacked from bf16 pairs once and shared by the R rows of a wave.
+__device__ __forceinline__ u32x2 ldw8(const int8_t* p) {
+#if defined(ARIA_EMU) || !ARIA_DECODE_NT
+    return *reinterpret_cast<const u32x2*>(p);
+#else
+    return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+#endif
+}
+__device__ __forceinline__ f32x2 codes_lo(uint32_t u) { return f32x2{float(u & 0xffu), float((u >> 8) & 0xffu)} - f32x2{128.f, 128.f}; }
+__device__ __forceinline__ f32x2 codes_hi(uint32_t u) { return f32x2{float((u >> 16) & 0xffu), float(u >> 24)} - f32x2{128.f, 128.f}; }
+// acc (two fp32 partial sums) += the 8 codes of w . the 8 activations xf (unpacked: xf[2 q] = pair q of the bf16 chunk)
+__device__ __forceinline__ f32x2 dot8q(u32x2 w, const f32x2 (&xf)[4], f32x2 acc) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t u = w[h] ^ 0x80808080u;
+        acc = __builtin_elementwise_fma(codes_lo(u), xf[2 * h], acc);
+        acc = __builtin_elementwise_fma(codes_hi(u), xf[2 * h + 1], acc);
+    }
+    return acc;
+}
+__device__ __forceinline__ void unpack_chunk(f32x2 (&xf)[4], const u32x4& x) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xf[q] = f32x2{bflo(x[q]), bfhi(x[q])};
+}
+// R consecutive code rows as 8-byte chunks c = l + 64 i per lane (load_rows' clamping: no branches, every load of the wave in flight together)
+template <int R, int NC>
+__device__ __forceinline__ void load_rows_q(u32x2 (&a)[R][NC], const int8_t* w, long long ldw, int row0, int nrows, int K, int l) {
+    const int nch = K >> 3;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int8_t* row = w + (long long)min(row0 + r, nrows - 1) * ldw;
+#pragma unroll
+        for (int i = 0; i < NC; ++i) a[r][i] = ldw8(row + min(l + 64 * i, nch - 1) * 8);
+    }
+}
+template <int R>
+__device__ __forceinline__ void load_scales(float (&sc)[R], const bf16_t* s, int row0, int nrows) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) sc[r] = bf2f(s[min(row0 + r, nrows - 1)]);
+}
+// acc[r] = s[r] * (row r . x), every lane holds the full sums
+template <int R, int NC>
+__device__ __forceinline__ void dot_loaded_q(float (&acc)[R], const u32x2 (&a)[R][NC], const float (&sc)[R], const u32x4 (&xv)[NC]) {
+    f32x2 s[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) s[r] = f32x2{0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        f32x2 xf[4];
+        unpack_chunk(xf, xv[i]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) s[r] = dot8q(a[r][i], xf, s[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = sc[r] * wave_sum_bcast(s[r].x + s[r].y);
+}
+
+// gemv_kernel on int8 rows: y[n] = bf16(s[n] * (Q[n,:] . xn)) (+ residual[n], added to the rounded product)
+template <int R, int NC>
+__global__ __launch_bounds__(256) void gemv_w8_kernel(const int8_t* W, const bf16_t* S, long long ldw, const bf16_t* x, const bf16_t* norm_w,
+                                                      float eps, int K, int N, const bf16_t* residual, bf16_t* y) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int row0 = (blockIdx.x * 4 + w) * R;
+    if (row0 >= N) return;
+    u32x4 xv[NC];
+    u32x2 a[R][NC];
+    float sc[R], acc[R];
+    load_rows_q<R, NC>(a, W, ldw, row0, N, K, l);
+    load_scales<R>(sc, S, row0, N);
+    load_vector<NC>(xv, x, norm_w, eps, K, l);
+    dot_loaded_q<R, NC>(acc, a, sc, xv);
+    if (l == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (row0 + r < N) y[row0 + r] = residual ? f2bf(bf2f(residual[row0 + r]) + rbf(acc[r])) : f2bf(acc[r]);
+    }
+}
+
+// router_shared_up_kernel with int8 shared rows: blocks [0, nrb) the E router logits from the bf16 gate (gemv_kernel<2, NC>'s rows and order),
+// the rest the shared expert's SwiGLU activations act_s[n] = bf16(bf16(silu(bf16(s1 Q1[n,:] . xn))) * bf16(s3 Q3[n,:] . xn))
+template <int R, int NC>
+__global__ __launch_bounds__(256) void router_shared_up_w8_kernel(const bf16_t* gate, int E, bf16_t* logits, const int8_t* S1, const bf16_t* SS1,
+                                                                  const int8_t* S3, const bf16_t* SS3, int rows_s, const bf16_t* x,
+                                                                  const bf16_t* norm_w, float eps, int K, bf16_t* act_s, int nrb) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    u32x4 xv[NC];
+    if (int(blockIdx.x) < nrb) {  // block-uniform
+        const int row0 = (blockIdx.x * 4 + w) * 2;
+        if (row0 >= E) return;
+        float acc[2];
+        u32x4 a[2][NC];
+        load_rows<2, NC>(a, gate, K, row0, E, K, l);
+        load_vector<NC>(xv, x, norm_w, eps, K, l);
+        dot_loaded<2, NC>(acc, a, xv);
+        if (l == 0) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                if (row0 + r < E) logits[row0 + r] = f2bf(acc[r]);
+        }
+        return;
+    }
+    const int row0 = ((int(blockIdx.x) - nrb) * 4 + w) * R;
+    if (row0 >= rows_s) return;
+    float a1[R], a3[R], c1[R], c3[R];
+    u32x2 r1[R][NC], r3[R][NC];
+    load_rows_q<R, NC>(r1, S1, K, row0, rows_s, K, l);
+    load_rows_q<R, NC>(r3, S3, K, row0, rows_s, K, l);
+    load_scales<R>(c1, SS1, row0, rows_s);
+    load_scales<R>(c3, SS3, row0, rows_s);
+    load_vector<NC>(xv, x, norm_w, eps, K, l);
+    dot_loaded_q<R, NC>(a1, r1, c1, xv);
+    dot_loaded_q<R, NC>(a3, r3, c3, xv);
+    if (l == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (row0 + r < rows_s) act_s[row0 + r] = f2bf(rbf(silu(rbf(a1[r]))) * rbf(a3[r]));
+    }
+}
+
+// expert_up_kernel on int8 experts (the k routed slices only: the shared expert rides with the router): routing in front, then every code row
+// of the wave, then the vector.  Q1 / Q3 [E, I, K], scales SC1 / SC3 [E, I].
+template <int R, int NC>
+__global__ __launch_bounds__(256) void expert_up_w8_kernel(const int8_t* W1, const bf16_t* SC1, const int8_t* W3, const bf16_t* SC3,
+                                                           const bf16_t* logits, int E, bf16_t* scores, int32_t* idx, int k, const bf16_t* x,
+                                                           const bf16_t* norm_w, float eps, int K, int I, bf16_t* act) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, j = blockIdx.y;
+    const int row0 = (blockIdx.x * 4 + w) * R;
+    if (row0 >= I) return;
+    float my_score;
+    int my_idx;
+    const int e = route_one_token(logits, E, k, l, j, my_score, my_idx);
+    if (blockIdx.x == 0 && j == 0 && w == 0 && l < k) {
+        scores[l] = f2bf(my_score);
+        idx[l] = my_idx;
+    }
+    u32x4 xv[NC];
+    u32x2 r1[R][NC], r3[R][NC];
+    float a1[R], a3[R], c1[R], c3[R];
+    load_rows_q<R, NC>(r1, W1 + (long long)e * I * K, K, row0, I, K, l);
+    load_rows_q<R, NC>(r3, W3 + (long long)e * I * K, K, row0, I, K, l);
+    load_scales<R>(c1, SC1 + (long long)e * I, row0, I);
+    load_scales<R>(c3, SC3 + (long long)e * I, row0, I);
+    load_vector<NC>(xv, x, norm_w, eps, K, l);
+    dot_loaded_q<R, NC>(a1, r1, c1, xv);
+    dot_loaded_q<R, NC>(a3, r3, c3, xv);
+    if (l == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (row0 + r < I) act[(long long)j * I + row0 + r] = f2bf(rbf(silu(rbf(a1[r]))) * rbf(a3[r]));
+    }
+}
+
+// expert_down_combine_kernel on int8 rows (Q2 [E, N, I] with scales SC2 [E, N]; shared Q2s [N, ns I] with SS2 [N]): the same LDS activation
+// images, the same epilogue roundings -- eo_j = bf16(s2 * dot), out = bf16(h + bf16(bf16(sum_j bf16(eo_j score_j)) + bf16(ss2 * dot_s)))
+template <int NCI, int NCS>
+__global__ __launch_bounds__(256) void expert_down_combine_w8_kernel(const int8_t* W2, const bf16_t* SC2, const int8_t* S2, const bf16_t* SS2,
+                                                                     const int32_t* idx, const bf16_t* scores, int k, int ns, const bf16_t* act,
+                                                                     int I, int N, const bf16_t* h, bf16_t* out) {
+    ARIA_DYN_SMEM(smem);
+    u32x4* sa = reinterpret_cast<u32x4*>(smem);  // [k][NCI * 64] routed images, then [NCS * 64] the shared expert's
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    const int nchI = I >> 3, nchS = (ns * I) >> 3;
+    const int n = blockIdx.x * 4 + w, nn = min(n, N - 1);
+    const int ninstr = k * NCI + NCS;
+    for (int g = w; g < ninstr; g += 4) {
+        const bf16_t* src;
+        if (g < k * NCI) {
+            const int j = g / NCI, cc = (g % NCI) * 64 + l;
+            src = cc < nchI ? act + (long long)j * I + cc * 8 : reinterpret_cast<const bf16_t*>(decode_zero_page) + 8 * (l & 15);
+        } else {
+            const int cc = (g - k * NCI) * 64 + l;
+            src = cc < nchS ? act + (long long)k * I + cc * 8 : reinterpret_cast<const bf16_t*>(decode_zero_page) + 8 * (l & 15);
+        }
+        glds16(src, sa + 64 * g);
+    }
+    int my_e = 0, my_sc = 0;
+    if (l < k) {
+        my_e = idx[l];
+        my_sc = int(uint32_t(scores[l]) << 16);
+    }
+    int e[DOWN_KMAX];
+    float sc[DOWN_KMAX], rs[DOWN_KMAX];
+#pragma unroll
+    for (int j = 0; j < DOWN_KMAX; ++j) {
+        e[j] = read_lane(my_e, j);
+        sc[j] = __builtin_bit_cast(float, read_lane(my_sc, j));
+    }
+    u32x2 wr[DOWN_KMAX][NCI], ws[NCS];
+    {
+        const int8_t* row = S2 + (long long)nn * ns * I;
+#pragma unroll
+        for (int i = 0; i < NCS; ++i) ws[i] = ldw8(row + min(l + 64 * i, nchS - 1) * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < DOWN_KMAX; ++j)
+        if (j < k) {
+            const int8_t* row = W2 + ((long long)e[j] * N + nn) * I;
+#pragma unroll
+            for (int i = 0; i < NCI; ++i) wr[j][i] = ldw8(row + min(l + 64 * i, nchI - 1) * 8);
+        }
+#pragma unroll
+    for (int j = 0; j < DOWN_KMAX; ++j) rs[j] = j < k ? bf2f(SC2[(long long)e[j] * N + nn]) : 0.f;
+    const float rss = bf2f(SS2[nn]);
+    wait_vm<0>();
+    sync();
+    float accs = 0.f;
+#pragma unroll
+    for (int j = 0; j < DOWN_KMAX; ++j)
+        if (j < k) {
+            f32x2 s = {0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < NCI; ++i) {
+                f32x2 xf[4];
+                unpack_chunk(xf, sa[j * NCI * 64 + l + 64 * i]);
+                s = dot8q(wr[j][i], xf, s);
+            }
+            const float d = rs[j] * wave_sum_bcast(s.x + s.y);
+            accs += rbf(rbf(d) * sc[j]);
+        }
+    f32x2 s = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NCS; ++i) {
+        f32x2 xf[4];
+        unpack_chunk(xf, sa[k * NCI * 64 + l + 64 * i]);
+        s = dot8q(ws[i], xf, s);
+    }
+    const float sh = rss * wave_sum_bcast(s.x + s.y);
+    if (l == 0 && n < N) out[n] = f2bf(bf2f(h[n]) + rbf(rbf(accs) + rbf(sh)));
+}
+
+// out[r, c] = bf16(float(q[r, c]) * float(s[r])) -- 8 codes per thread and step (8-byte loads, 16-byte stores) when C % 8 == 0
+__global__ __launch_bounds__(256) void dequant_w8_kernel(const int8_t* q, const bf16_t* s, bf16_t* out, long long rows, long long C) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long nch = rows * (C >> 3);
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < nch; c += stride) {
+        const long long e0 = c * 8;
+        const float sc = bf2f(s[e0 / C]);
+        const u32x2 v = *reinterpret_cast<const u32x2*>(q + e0);
+        u32x4 o;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const uint32_t wd = v[p >> 1] >> (16 * (p & 1));
+            o[p] = pack2bf(float(int8_t(wd & 0xffu)) * sc, float(int8_t((wd >> 8) & 0xffu)) * sc);
+        }
+        st16(out + e0, o);
+    }
+}
+__global__ __launch_bounds__(256) void dequant_w8_any_kernel(const int8_t* q, const bf16_t* s, bf16_t* out, long long rows, long long C) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += stride) out[i] = f2bf(float(q[i]) * bf2f(s[i / C]));
+}
+
+int launch_gemv_w8(int N, void* stream, const int8_t* W, const bf16_t* S, long long ldw, const bf16_t* x, const bf16_t* norm_w, float eps,
+                   int K, const bf16_t* residual, bf16_t* y) {
+    // rows per wave as launch_gemv, plus 8 for the output head (100 K rows: still > 3000 waves, twice the code bytes in flight per wave)
+    if (N >= 32768) {
+#define CALL(NC) ARIA_LAUNCH((gemv_w8_kernel<8, NC>), dim3((N + 31) / 32), dim3(256), 0, stream, W, S, ldw, x, norm_w, eps, K, N, residual, y)
+        ARIA_NC_SWITCH(chunks_per_lane(K), CALL)
+#undef CALL
+    } else if (N >= 4096) {
+#define CALL(NC) ARIA_LAUNCH((gemv_w8_kernel<4, NC>), dim3((N + 15) / 16), dim3(256), 0, stream, W, S, ldw, x, norm_w, eps, K, N, residual, y)
+        ARIA_NC_SWITCH(chunks_per_lane(K), CALL)
+#undef CALL
+    } else {
+#define CALL(NC) ARIA_LAUNCH((gemv_w8_kernel<2, NC>), dim3((N + 7) / 8), dim3(256), 0, stream, W, S, ldw, x, norm_w, eps, K, N, residual, y)
+        ARIA_NC_SWITCH(chunks_per_lane(K), CALL)
+#undef CALL
+    }
+    return aria_check_launch();
+}
+
+// the (NCI, NCS) instantiations of the fused down-projection (expert_down_combine_kernel's); 0 = none (the int8 engine declines the model)
+inline int w8_down_form(int ncI, int ncS) { return (ncI == 4 && ncS == 7) ? 47 : (ncI == 1 && ncS == 1) ? 11 : (ncI <= 2 && ncS <= 4) ? 24 : 0; }
+
 }  // namespace
 
 extern "C" {
@@ -1089,6 +1374,121 @@ void aria_decode_graph_destroy(void* handle) {
     if (g->graph) (void)hipGraphDestroy(g->graph);
 #endif
     delete g;
+}
+
+int aria_decode_token_w8(const void* const* ptrs, const int64_t* dims, float eps, void* stream) {
+    if (!ptrs || !dims) return ARIA_ERR_INVALID;
+    const int64_t L = dims[0], D = dims[1], H = dims[2], hd = dims[3], E = dims[4], k = dims[5], I = dims[6], Is = dims[7], V = dims[8],
+                  Smax = dims[9];
+    if (L <= 0 || D <= 0 || H * hd != D || (D & 7) || (I & 7) || (Is & 7) || D > 4096 || I > 4096 || Is > 4096 || E > 256)
+        return ARIA_ERR_UNSUPPORTED;
+    if (hd != 64 && hd != 128) return ARIA_ERR_UNSUPPORTED;
+    if (Is % I || k < 1 || k > DOWN_KMAX || k > E || !decode_fuse_enabled()) return ARIA_ERR_UNSUPPORTED;  // the fused schedule only
+    const int ns = int(Is / I), ncD = chunks_per_lane(D), ncI = chunks_per_lane(I), ncS = chunks_per_lane(Is);
+    const int down = w8_down_form(ncI, ncS);
+    if (!down) return ARIA_ERR_UNSUPPORTED;
+    for (int i = 0; i < ARIA_DECODE_W8_HEADER_PTRS + ARIA_DECODE_W8_LAYER_PTRS * L; ++i)
+        if (!ptrs[i]) return ARIA_ERR_INVALID;
+    const bf16_t* freqs = static_cast<const bf16_t*>(ptrs[0]);
+    const bf16_t* final_norm = static_cast<const bf16_t*>(ptrs[1]);
+    const int8_t* out_w = static_cast<const int8_t*>(ptrs[2]);
+    const Scratch s = carve(static_cast<char*>(const_cast<void*>(ptrs[3])), L, D, H, hd, E, k, I, Is);
+    const int32_t* pos = static_cast<const int32_t*>(ptrs[4]);
+    const bf16_t* x = static_cast<const bf16_t*>(ptrs[5]);
+    bf16_t* logits = static_cast<bf16_t*>(const_cast<void*>(ptrs[6]));
+    const bf16_t* out_s = static_cast<const bf16_t*>(ptrs[8]);
+    int rc;
+#define ARIA_TRY(call)              \
+    do {                            \
+        rc = (call);                \
+        if (rc != ARIA_OK) return rc; \
+    } while (0)
+    for (int64_t li = 0; li < L; ++li) {
+        const void* const* lp = ptrs + ARIA_DECODE_W8_HEADER_PTRS + ARIA_DECODE_W8_LAYER_PTRS * li;
+        auto B = [&](int i) { return static_cast<const bf16_t*>(lp[i]); };
+        auto Q = [&](int i) { return static_cast<const int8_t*>(lp[i]); };
+        bf16_t *kc = static_cast<bf16_t*>(const_cast<void*>(lp[19])), *vc = static_cast<bf16_t*>(const_cast<void*>(lp[20]));
+        bf16_t* h = s.xa;
+        bf16_t *const rl = s.rl + li * s.rl_stride, *const scores = s.scores + li * s.sc_stride;
+        int32_t* const idx = s.idx + li * s.idx_stride;
+        // attention block: h = x + wo( attn( rope(wqkv(norm(x))) ) )
+        ARIA_TRY(launch_gemv_w8(int(3 * D), stream, Q(1), B(2), (long long)D, x, B(0), eps, int(D), nullptr, s.qkv));
+        const int splits = decode_splits_for(Smax);
+        if (Smax <= 16384 || splits > 1) {
+            ARIA_TRY(launch_decode_attn(stream, (const bf16_t*)s.qkv, freqs, pos, kc, vc, s.ao, s.part, H, hd, D, splits));
+        } else {
+            ARIA_LAUNCH(rope_cache_kernel, dim3(unsigned((3 * D / 8 + 255) / 256)), dim3(256), 0, stream, s.qkv, freqs, pos, kc, vc, int(D),
+                        int(hd), s.kv_len);
+            ARIA_TRY(aria_check_launch());
+            ARIA_TRY(aria_attn_fwd(s.qkv, kc, vc, s.ao, nullptr, s.kv_len, nullptr, 1, 1, Smax, H, hd, D, D, D, D, 1.0f / sqrtf(float(hd)),
+                                   0, stream));
+        }
+        ARIA_TRY(launch_gemv_w8(int(D), stream, Q(3), B(4), (long long)D, s.ao, nullptr, 0.f, int(D), x, h));
+        // MoE block: router logits + shared up | routed up (top-k inside) | all down-projections + combine + residual
+        const int nrb = int((E + 7) / 8);
+#define CALL(NC)                                                                                                                            \
+    ARIA_LAUNCH((router_shared_up_w8_kernel<2, NC>), dim3(unsigned(nrb + (Is + 7) / 8)), dim3(256), 0, stream, B(6), int(E), rl, Q(13), B(14), \
+                Q(15), B(16), int(Is), (const bf16_t*)h, B(5), eps, int(D), s.act + k * I, nrb)
+        ARIA_NC_SWITCH(ncD, CALL)
+#undef CALL
+        if (I * k >= 8192) {
+#define CALL(NC)                                                                                                                     \
+    ARIA_LAUNCH((expert_up_w8_kernel<4, NC>), dim3(unsigned((I + 15) / 16), unsigned(k)), dim3(256), 0, stream, Q(7), B(8), Q(9), B(10), \
+                (const bf16_t*)rl, int(E), scores, idx, int(k), (const bf16_t*)h, B(5), eps, int(D), int(I), s.act)
+            ARIA_NC_SWITCH(ncD, CALL)
+#undef CALL
+        } else {
+#define CALL(NC)                                                                                                                    \
+    ARIA_LAUNCH((expert_up_w8_kernel<2, NC>), dim3(unsigned((I + 7) / 8), unsigned(k)), dim3(256), 0, stream, Q(7), B(8), Q(9), B(10), \
+                (const bf16_t*)rl, int(E), scores, idx, int(k), (const bf16_t*)h, B(5), eps, int(D), int(I), s.act)
+            ARIA_NC_SWITCH(ncD, CALL)
+#undef CALL
+        }
+#define DOWNC(NCI, NCS)                                                                                                                  \
+    ARIA_LAUNCH((expert_down_combine_w8_kernel<NCI, NCS>), dim3(unsigned((D + 3) / 4)), dim3(256), size_t(k * NCI + NCS) * 1024, stream, \
+                Q(11), B(12), Q(17), B(18), (const int32_t*)idx, (const bf16_t*)scores, int(k), ns, (const bf16_t*)s.act, int(I), int(D),  \
+                (const bf16_t*)h, s.xb)
+        if (down == 47) {  // Aria: I = 1664, shared 3328
+            DOWNC(4, 7);
+        } else if (down == 11) {
+            DOWNC(1, 1);
+        } else {
+            DOWNC(2, 4);
+        }
+#undef DOWNC
+        ARIA_TRY(aria_check_launch());
+        x = s.xb;
+    }
+    ARIA_TRY(launch_gemv_w8(int(V), stream, out_w, out_s, (long long)D, x, final_norm, eps, int(D), nullptr, logits));
+#undef ARIA_TRY
+    return ARIA_OK;
+}
+
+int aria_dequant_w8_bf16(const void* q, const void* scales, void* out, int64_t rows, int64_t cols, void* stream) {
+    if (!q || !scales || !out || rows < 0 || cols <= 0) return ARIA_ERR_INVALID;
+    if (rows == 0) return ARIA_OK;
+    const long long n = rows * cols;
+    const bool vec = !(cols & 7) && !(reinterpret_cast<uintptr_t>(q) & 7) && !(reinterpret_cast<uintptr_t>(out) & 15);
+    const long long work = vec ? n / 8 : n;
+    const unsigned grid = unsigned(std::min<long long>((work + 255) / 256, 16384));
+    if (vec)
+        ARIA_LAUNCH(dequant_w8_kernel, dim3(grid), dim3(256), 0, stream, static_cast<const int8_t*>(q), static_cast<const bf16_t*>(scales),
+                    static_cast<bf16_t*>(out), (long long)rows, (long long)cols);
+    else
+        ARIA_LAUNCH(dequant_w8_any_kernel, dim3(grid), dim3(256), 0, stream, static_cast<const int8_t*>(q), static_cast<const bf16_t*>(scales),
+                    static_cast<bf16_t*>(out), (long long)rows, (long long)cols);
+    return aria_check_launch();
+}
+
+int aria_gemv_w8(const void* q, const void* scales, const void* x, const void* norm_w, float eps, const void* residual, void* y, int64_t N,
+                 int64_t K, void* stream) {
+    if (!q || !scales || !x || !y || N <= 0 || K <= 0) return ARIA_ERR_INVALID;
+    if ((K & 7) || K > 4096 || N >= (1ll << 31)) return ARIA_ERR_UNSUPPORTED;  // 8-element chunks, at most 8 per lane
+    if ((reinterpret_cast<uintptr_t>(q) & 7) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(norm_w) & 15))
+        return ARIA_ERR_ALIGN;
+    return launch_gemv_w8(int(N), stream, static_cast<const int8_t*>(q), static_cast<const bf16_t*>(scales), (long long)K,
+                          static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(norm_w), eps, int(K), static_cast<const bf16_t*>(residual),
+                          static_cast<bf16_t*>(y));
 }
 
 }  // extern "C"

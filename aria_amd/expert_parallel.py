@@ -136,6 +136,8 @@ class AllToAllRowsFn(torch.autograd.Function):
 # --------------------------------------------------------------------------------------------- the EP MoE block
 def shard_expert_weights(fc1: torch.Tensor, fc2: torch.Tensor, rank: int, world: int):
     """Views of the local experts' weights ([E/W, D, 2I], [E/W, I, D])."""
+    if fc1.dtype == torch.int8 or fc2.dtype == torch.int8:
+        raise NotImplementedError("expert parallelism: int8 weight-only quantized experts are inference only")
     per = fc1.shape[0] // world
     return fc1[rank * per:(rank + 1) * per], fc2[rank * per:(rank + 1) * per]
 

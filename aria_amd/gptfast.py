@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as Fn
-from . import hip, ops
+from . import hip, ops, quantize
 from .vision import AriaProjector, AriaVisionConfig, AriaVisionModel
 
 bf16 = torch.bfloat16
@@ -252,6 +252,7 @@ class Transformer(nn.Module):
         self.decode_graph = False         # ... optionally replayed from a natively captured HIP graph (measured SLOWER than the plain
         #                                   enqueue on ROCm 7.2: 6.2 vs 4.8 ms/token -- graph kernel nodes cost more than stream launches)
         self._engine: Optional["DecodeEngine"] = None
+        self._w8 = False                  # int8 weight-only codes + row scales (aria_amd/quantize.py): inference only
         # bumped by whatever may re-home a weight (module.to / .cuda / casts; load_state_dict, also through a parent module, also assign=True):
         # the decode engine re-checks its whole pointer table only then
         self._weights_version = 0
@@ -266,6 +267,8 @@ class Transformer(nn.Module):
 
     def _engine_capable(self) -> bool:
         """The one-call-per-token engine serves this model's shape (native head dims of the decode attention kernel)."""
+        if self._w8 and not quantize.engine_serves(self.config):
+            return False
         return self.layers[0].attention.hdp == self.config.head_dim and self.config.head_dim in (64, 128)
 
     def _engine_ok(self) -> bool:
@@ -293,6 +296,8 @@ class Transformer(nn.Module):
         self.freqs_cis = precompute_freqs_cis(max(self.config.block_size, self.max_seq_length), self.config.head_dim,
                                               self.config.rope_base).to(dev).contiguous()
         for b in self.layers:  # gate / up pairs into one allocation each NOW (the decode engine records parameter addresses later)
+            if self._w8:   # (int8 codes: the dequantizing forward lays its bf16 pairs out adjacently itself)
+                break
             ff = b.feed_forward
             _glu_pair_ready(ff.cond_ffn.w1, ff.cond_ffn.w3)
             _glu_pair_ready(ff.shared_ffn.w1.weight, ff.shared_ffn.w3.weight)
@@ -321,6 +326,8 @@ class Transformer(nn.Module):
             pos32 = input_pos.to(torch.int32).reshape(-1).expand(B).contiguous()
             kv_len = pos32 + 1
         res, delta = x2d, None
+        if self._w8:
+            return self._forward_w8(res, B, S, pos32, kv_len, prefill, pos_is_arange, last_only)
         for layer in self.layers:
             res, delta = layer(res, delta, B, S, self.freqs_cis, pos32, kv_len, prefill, pos_is_arange)
         h = ops.rmsnorm(delta, self.norm.weight, self.norm.eps, residual=res, want_rstd=False)[0] if delta is not None else self.norm(res)
@@ -328,6 +335,21 @@ class Transformer(nn.Module):
             h = h.view(B, S, D)[:, -1].contiguous()
             return ops.gemm(h, self.output.weight).view(B, 1, -1)
         return ops.gemm(h, self.output.weight).view(B, S, -1)
+
+    def _forward_w8(self, res, B, S, pos32, kv_len, prefill, pos_is_arange, last_only):
+        """Every forward of an int8 model that the int8 engine does not take (prefill, B > 1, ``use_decode_engine = False``, shapes the
+        engine declines): before a layer runs, its codes are expanded into ONE bf16 scratch sized for a layer (quantize.dequantized_layer)
+        and the bf16 tile kernels run on views of it.  A correctness path, not a fast one: a B > 1 decode step pays a full dequant of every
+        layer (~2.6 GB of traffic per layer at Aria's widths).  The ``last_only`` head is an int8 GEMV per row."""
+        D = self.config.dim
+        delta = None
+        for layer in self.layers:
+            with quantize.dequantized_layer(self, layer):
+                res, delta = layer(res, delta, B, S, self.freqs_cis, pos32, kv_len, prefill, pos_is_arange)
+        h = ops.rmsnorm(delta, self.norm.weight, self.norm.eps, residual=res, want_rstd=False)[0]
+        if last_only:
+            return quantize.head_logits(self, h.view(B, S, D)[:, -1].contiguous(), True).view(B, 1, -1)
+        return quantize.head_logits(self, h, False).view(B, S, -1)
 
 
 class DecodeEngine:
@@ -346,6 +368,7 @@ class DecodeEngine:
         if att0.hdp != c.head_dim or c.head_dim not in (64, 128):
             raise RuntimeError("DecodeEngine: head_dim must be 64 or 128 (native attention head dims)")
         dev = model.output.weight.device
+        self.w8 = model._w8   # int8 weights: aria_decode_token_w8 on its own pointer table (no graph form)
         Is = c.intermediate_size * c.num_shared_experts
         self.dims = np.array([c.n_layer, c.dim, c.n_head, c.head_dim, c.num_experts, c.router_topk, c.intermediate_size, Is, c.vocab_size,
                               model.max_seq_length], dtype=np.int64)
@@ -367,7 +390,7 @@ class DecodeEngine:
         self._cheap = self._cheap_key(model)
         self.ptrs = (ctypes.c_void_p * len(tensors))(*self._addr)
         # one graph launch per token instead of ~13 launches per layer (None: capture failed or disabled -> plain enqueue)
-        self.graph = lib.cdll.aria_decode_graph_create(self.ptrs, self._dims_p, self.eps) if model.decode_graph else None
+        self.graph = lib.cdll.aria_decode_graph_create(self.ptrs, self._dims_p, self.eps) if model.decode_graph and not self.w8 else None
 
     def __del__(self):
         try:
@@ -378,12 +401,26 @@ class DecodeEngine:
 
     def _table(self, model: "Transformer"):
         """The pointer table of aria_decode_token, read from the MODEL's current tensors (weights, freqs_cis, KV cache) + the engine's own."""
+        if self.w8:
+            return self._table_w8(model)
         tensors = [model.freqs_cis, model.norm.weight, model.output.weight, self.scratch, self.pos, self.x_in, self.logits, self.pos]
         for blk in model.layers:
             a, f = blk.attention, blk.feed_forward
             tensors += [blk.attention_norm.weight, a.wqkv.weight, a.wo.weight, blk.ffn_norm.weight, f.gate.weight, f.cond_ffn.w1,
                         f.cond_ffn.w3, f.cond_ffn.w2, f.shared_ffn.w1.weight, f.shared_ffn.w3.weight, f.shared_ffn.w2.weight,
                         a.kv_cache.k, a.kv_cache.v]
+        return tensors
+
+    def _table_w8(self, model: "Transformer"):
+        """aria_decode_token_w8's table (include/aria_hip.h: ARIA_DECODE_W8_*_PTRS)"""
+        tensors = [model.freqs_cis, model.norm.weight, model.output.weight, self.scratch, self.pos, self.x_in, self.logits, self.pos,
+                   model.output.scales]
+        for blk in model.layers:
+            a, f = blk.attention, blk.feed_forward
+            cf, sf = f.cond_ffn, f.shared_ffn
+            tensors += [blk.attention_norm.weight, a.wqkv.weight, a.wqkv.scales, a.wo.weight, a.wo.scales, blk.ffn_norm.weight, f.gate.weight,
+                        cf.w1, cf.scales1, cf.w3, cf.scales3, cf.w2, cf.scales2, sf.w1.weight, sf.w1.scales, sf.w3.weight, sf.w3.scales,
+                        sf.w2.weight, sf.w2.scales, a.kv_cache.k, a.kv_cache.v]
         return tensors
 
     def valid_for(self, model: "Transformer") -> bool:
@@ -436,7 +473,7 @@ class DecodeEngine:
         if self.graph:
             self._lib.call("aria_decode_graph_launch", self.graph, stream)
         else:
-            self._lib.call("aria_decode_token", self.ptrs, self._dims_p, self.eps, stream)
+            self._lib.call("aria_decode_token_w8" if self.w8 else "aria_decode_token", self.ptrs, self._dims_p, self.eps, stream)
         return self.logits.view(1, 1, -1)
 
 
@@ -594,7 +631,21 @@ def generate(model: Aria, input_ids: torch.Tensor, max_new_tokens: int, *, pixel
 
 def load_model_pth(model: Aria, state_dict: dict, strict: bool = False):
     """Load a gptfast ``model.pth`` state dict (convert_hf_checkpoint.py output: ``llm.*`` gptfast names, vision / projector HF
-    names) -- tensors are copied as they are, no layout conversion."""
+    names) -- tensors are copied as they are, no layout conversion.  An int8 weight-only state dict (``*.scales`` keys: aria_amd/quantize.py,
+    ``model_int8.pth``) first turns the model into the quantized structure; its codes and scales are then copied verbatim, and any dtype or
+    shape mismatch raises."""
+    if quantize.is_int8_state_dict(state_dict):
+        quantize.convert_structure_(model)
+        own = model.state_dict()
+        for k, v in own.items():
+            if k in state_dict and (state_dict[k].dtype != v.dtype or state_dict[k].shape != v.shape):
+                raise ValueError(f"{k}: checkpoint has {state_dict[k].dtype} {tuple(state_dict[k].shape)}, the model {v.dtype} {tuple(v.shape)}")
+    elif quantize.is_quantized(model):
+        raise ValueError("load_model_pth: a bf16 state dict cannot be loaded into an int8-quantized model")
+    else:
+        bad = [k for k, v in state_dict.items() if v.dtype == torch.int8]
+        if bad:
+            raise ValueError(f"load_model_pth: int8 tensors {bad[:3]} without their *.scales keys (an incomplete int8 checkpoint)")
     own = model.state_dict()
     missing = [k for k in own if k not in state_dict]
     if strict and missing:

@@ -23,12 +23,17 @@ class GenerationConfig:
 
 class ModelConfig:
     def __init__(self, checkpoint_path, device: str = "cuda", precision: torch.dtype = torch.bfloat16, compile: bool = False,
-                 compile_prefill: bool = False, apply_regional_compilation: bool = False):
+                 compile_prefill: bool = False, apply_regional_compilation: bool = False, model_args: Optional[G.ModelArgs] = None,
+                 vision_config=None):
+        """``checkpoint_path``: a ``model.pth`` or an int8 ``model_int8.pth`` (aria_amd.quantize); ``precision`` is the compute dtype (bf16
+        for both).  ``model_args`` / ``vision_config``: the LM's / the vision tower's shape when it is not Aria's."""
         self.checkpoint_path, self.device, self.precision = Path(checkpoint_path), device, precision
+        self.model_args, self.vision_config = model_args, vision_config
         self.compile, self.compile_prefill, self.apply_regional_compilation = compile, compile_prefill, apply_regional_compilation
 
 
-def load_model_and_processor(checkpoint_path: Path, device, precision=torch.bfloat16, model_args: Optional[G.ModelArgs] = None, processor=None):
+def load_model_and_processor(checkpoint_path: Path, device, precision=torch.bfloat16, model_args: Optional[G.ModelArgs] = None, processor=None,
+                             vision_config=None):
     """``model.pth`` (convert_hf_checkpoint.py / aria_amd.checkpoint.convert_hf_checkpoint) -> ``Aria`` on ``device``; the processor comes
     from the tokenizer files next to it (generate.py:218-220) unless one is handed in."""
     if precision != torch.bfloat16:
@@ -36,7 +41,7 @@ def load_model_and_processor(checkpoint_path: Path, device, precision=torch.bflo
     prev = torch.get_default_device() if hasattr(torch, "get_default_device") else None
     torch.set_default_device(device)
     try:
-        model = G.Aria(model_args or G.ModelArgs())
+        model = G.Aria(model_args or G.ModelArgs(), vision_config=vision_config)
     finally:
         torch.set_default_device(prev if prev is not None else "cpu")
     G.load_model_pth(model, torch.load(str(checkpoint_path), map_location="cpu", mmap=True, weights_only=True), strict=True)
@@ -59,7 +64,8 @@ class Generator:
         self._decoder = None
         if self.model is None:
             self.model, self.processor = load_model_and_processor(model_config.checkpoint_path, model_config.device, model_config.precision,
-                                                                  processor=processor)
+                                                                  getattr(model_config, "model_args", None), processor=processor,
+                                                                  vision_config=getattr(model_config, "vision_config", None))
 
     def _stops(self):
         """single-token stop strings become a device-side comparison; anything longer keeps the reference's decode-and-compare callback"""

@@ -42,6 +42,9 @@ SIGNATURES = {
     "aria_decode_graph_create": [P, P, F32],
     "aria_decode_graph_launch": [P, P],
     "aria_decode_graph_destroy": [P],
+    "aria_decode_token_w8": [P, P, F32, P],
+    "aria_dequant_w8_bf16": [P, P, P, I64, I64, P],
+    "aria_gemv_w8": [P, P, P, P, F32, P, P, I64, I64, P],
     "aria_gemm_bf16": [P, P, P, P, I64, I64, I64, I32, I32, I64, I64, I64, I32, I32, P],
     "aria_gemm_bf16_ws": [P, P, P, P, I64, I64, I64, I32, I32, I64, I64, I64, I32, I32, P, I64, P],
     "aria_gemm_workspace_bytes": [I64, I64, I64, I32, I32],

@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from .moe_lm import GroupedGEMM, Linear
+from .quantize import reject_quantized
 
 
 class GroupedGemmLoraLayer(nn.Module):
@@ -158,6 +159,7 @@ def apply_lora_to_experts(model: nn.Module, r: int = 8, lora_alpha: int = 16, lo
                           target_suffixes: Iterable[str] = ("experts.fc1", "experts.fc2")) -> nn.Module:
     """Freeze every parameter, wrap each ``GroupedGEMM`` whose qualified name ends with one of ``target_suffixes`` (the recipe's
     ``lora_target_modules`` for the experts, aria/train.py:100-112) and leave only the LoRA factors trainable."""
+    reject_quantized(model, "LoRA")
     for p in model.parameters():
         p.requires_grad_(False)
     targets = [(name, mod) for name, mod in model.named_modules()
@@ -195,6 +197,7 @@ def apply_lora_from_config(model: nn.Module, cfg) -> list:
     get a ``GroupedGemmLoraLayer`` and the ``Linear`` projections of the language model (q/k/v/o_proj, shared experts, lm_head) a
     ``LinearLoraLayer``; everything else is frozen.  Returned: the selected names that were NOT adapted (``nn.Linear`` modules of the
     projector / vision tower when the recipe does not freeze them: their blocks have no module-by-module path here)."""
+    reject_quantized(model, "LoRA")
     names = [n for n, _ in model.named_modules()]
     targets = get_lora_target_modules(names, cfg)
     r, alpha, drop = int(cfg.get("lora_r", 8)), int(cfg.get("lora_alpha", 32)), float(cfg.get("lora_dropout", 0.0))

@@ -486,6 +486,48 @@ def sample_topk(logits: torch.Tensor, q: torch.Tensor, temperature: float, top_k
     return out
 
 
+def dequant_w8(q: torch.Tensor, scales: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Int8 weight-only codes -> bf16 (aria_dequant_w8_bf16): q int8 [..., C] with one bf16 scale per row (scales [...]) ->
+    out[r, c] = bf16(float(q[r, c]) * float(s[r])), the same bits as ``(q.float() * s.float()[..., None]).to(bfloat16)``."""
+    _chk(q, torch.int8, "q"), _chk(scales, bf16, "scales")
+    if not (q.is_contiguous() and scales.is_contiguous()) or q.dim() < 1 or tuple(scales.shape) != tuple(q.shape[:-1]) or q.numel() == 0:
+        raise ValueError(f"dequant_w8: need contiguous q {tuple(q.shape)} with one scale per row, got scales {tuple(scales.shape)}")
+    rows = scales.numel()
+    if out is None:
+        out = torch.empty(q.shape, dtype=bf16, device=q.device)
+    _chk(out, name="out")
+    if not out.is_contiguous() or out.numel() != q.numel():
+        raise ValueError("dequant_w8: out must be contiguous with q's element count")
+    hip.get_lib().call("aria_dequant_w8_bf16", _p(q), _p(scales), _p(out), rows, q.numel() // rows, _stream(q))
+    return out
+
+
+def gemv_w8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-5,
+            residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [N] = bf16(s[n] * (q[n, :] . xn)) (+ residual, added to the rounded product) on int8 rows (aria_gemv_w8): q int8 [N, K],
+    scales bf16 [N], x bf16 [K], xn = RMSNorm(x) * norm_w when ``norm_w`` is given.  K % 8 == 0, K <= 4096."""
+    _chk(q, torch.int8, "q"), _chk(scales, bf16, "scales"), _chk(x, name="x")
+    if q.dim() != 2 or not q.is_contiguous():
+        raise ValueError(f"gemv_w8: q must be a contiguous [N, K] tensor, got {tuple(q.shape)}")
+    N, K = q.shape
+    x = x.reshape(-1).contiguous()
+    if x.numel() != K or scales.numel() != N:
+        raise ValueError(f"gemv_w8: x [{x.numel()}] / scales [{scales.numel()}] do not fit q [{N}, {K}]")
+    if norm_w is not None:
+        _chk(norm_w, name="norm_w")
+        if norm_w.numel() != K or not norm_w.is_contiguous():
+            raise ValueError(f"gemv_w8: norm_w must be a contiguous [{K}] tensor")
+    if residual is not None:
+        _chk(residual, name="residual")
+        residual = residual.reshape(-1).contiguous()
+        if residual.numel() != N:
+            raise ValueError(f"gemv_w8: residual must have {N} elements")
+    if out is None:
+        out = torch.empty(N, dtype=bf16, device=q.device)
+    hip.get_lib().call("aria_gemv_w8", _p(q), _p(scales.contiguous()), _p(x), _p(norm_w), float(eps), _p(residual), _p(out), N, K, _stream(q))
+    return out
+
+
 def decode_route(logits: torch.Tensor, k: int):
     """The decode engine's routing of ONE token (csrc/decode.hip route_one_token) on its own: logits [E] bf16 -> (scores [k] bf16,
     idx [k] int32); the same function as ``moe_route`` on one row."""

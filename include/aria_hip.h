@@ -434,6 +434,30 @@ void* aria_decode_graph_create(const void* const* ptrs, const int64_t* dims, flo
 int aria_decode_graph_launch(void* graph, void* stream);
 void aria_decode_graph_destroy(void* graph);
 
+/* ------------------------------------------------------------------------------------------------
+ * Int8 weight-only form of the engine (decode.hip; weights written by aria_amd/quantize.py): symmetric codes q int8 with ONE bf16 scale
+ * per output row, w = q * s.  Same dims, scratch (aria_decode_scratch_bytes) and routing record (aria_decode_trace_layout) as
+ * aria_decode_token; the six-launch schedule only (ARIA_DECODE_FUSE=0, top_k > 6, or widths without a fused down-projection form:
+ * ARIA_ERR_UNSUPPORTED).  Every dot product is accumulated in fp32 over exact operands (code, bf16 activation) and scaled once,
+ * y = bf16(s * sum_k x_k q_k); the other rounding points are aria_decode_token's.  Router gate, norms and caches stay bf16.
+ * ptrs: [0..7] as aria_decode_token with [2] = output codes int8 [V, D], then [8] output scales bf16 [V];
+ *   then per layer (21 each): attention_norm [D], wqkv int8 [3D, D], wqkv scales [3D], wo int8 [D, D], wo scales [D], ffn_norm [D],
+ *   gate bf16 [E, D], cond_ffn.w1 int8 [E, I, D], scales1 [E, I], w3 int8 [E, I, D], scales3 [E, I], w2 int8 [E, D, I], scales2 [E, D],
+ *   shared_ffn.w1 int8 [Is, D], its scales [Is], shared w3 int8 [Is, D], its scales [Is], shared w2 int8 [D, Is], its scales [D],
+ *   k_cache [S_max, D], v_cache [S_max, D].  Code rows 8-byte aligned.
+ * ------------------------------------------------------------------------------------------------ */
+#define ARIA_DECODE_W8_HEADER_PTRS 9
+#define ARIA_DECODE_W8_LAYER_PTRS 21
+int aria_decode_token_w8(const void* const* ptrs, const int64_t* dims, float eps, void* stream);
+/* out bf16 [rows, cols] = bf16(float(q[r, c]) * float(scales[r])) (RNE; the same bits as (q.float() * s.float()).to(bfloat16)),
+ * q int8 [rows, cols] and out contiguous, any cols; codes -128 .. 127. */
+int aria_dequant_w8_bf16(const void* q, const void* scales, void* out, int64_t rows, int64_t cols, void* stream);
+/* y bf16 [N] = bf16(scales[n] * (q[n, :] . xn)) (+ residual[n], added to the rounded product in fp32 and rounded again), q int8 [N, K]
+ * contiguous (8-byte aligned), x bf16 [K] (16-byte aligned); xn = x, or RMSNorm(x) * norm_w when norm_w != NULL (16-byte aligned, eps).
+ * fp32 accumulation over exact operands.  K % 8 == 0 and K <= 4096, else ARIA_ERR_UNSUPPORTED. */
+int aria_gemv_w8(const void* q, const void* scales, const void* x, const void* norm_w, float eps, const void* residual, void* y, int64_t N,
+                 int64_t K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
