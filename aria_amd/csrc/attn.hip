@@ -206,225 +206,15 @@ __device__ __forceinline__ void tile2_store(const Chunks2<HD, NW>& r, bf16_t* s,
     }
 }
 
-template <int HD, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_fwd2_kernel(const bf16_t* Q, const bf16_t* K, const bf16_t* V, bf16_t* O, float* LSE,
-                                                        const int32_t* kv_len, const uint8_t* key_mask, int Sq, int S, int H,
-                                                        long long ldq, long long ldk, long long ldv, long long ldo, float scale,
-                                                        int causal, int nbatch) {
-    using C = Cfg2<HD, NW>;
-    ARIA_DYN_SMEM(smem);
-    bf16_t* sK = reinterpret_cast<bf16_t*>(smem);          // [2][64][KP]
-    bf16_t* sV = sK + 2 * 64 * C::KP;                      // [2][64][VP]
-    uint8_t* sM = reinterpret_cast<uint8_t*>(sV + 2 * 64 * C::VP);  // [2][64]
-    int* sFlag = reinterpret_cast<int*>(sM + 128);         // [2]
-    const int t = threadIdx.x, l = t & 63, w = t >> 6, h2 = l >> 5;
-    int qblk, head, b;
-    if (!attn_block_coords((Sq + C::QB - 1) / C::QB, H, nbatch, causal, true, qblk, head, b)) return;
-    const int q0 = qblk * C::QB;
-    const long long tok0 = (long long)b * S, tokq0 = (long long)b * Sq;
-    const bf16_t* Qb = Q + tokq0 * ldq + head * HD;
-    const bf16_t* Kb = K + tok0 * ldk + head * HD;
-    const bf16_t* Vb = V + tok0 * ldv + head * HD;
-    const uint8_t* kmb = key_mask ? key_mask + tok0 : nullptr;
-    const int q_wmin = q0 + 32 * w, q_abs = q_wmin + (l & 31);
-    const int klen = kv_len ? min(S, kv_len[b]) : S;
-    const float scale2 = scale * 1.4426950408889634f;
-
-    s16x8 qf[C::KS];
-#pragma unroll
-    for (int kk = 0; kk < C::KS; ++kk) {
-        u32x4 v = zero16();
-        const int col = kk * 16 + h2 * 8;
-        if (q_abs < Sq && col < HD) v = ld16(Qb + (long long)q_abs * ldq + col);
-        qf[kk] = __builtin_bit_cast(s16x8, v);
-    }
-#pragma unroll
-    for (int kk = 0; kk < C::KS; ++kk) settle(qf[kk]);  // (see settle(): keeps the wait for Q out of the key-tile loop)
-    f32x16 o[C::DT];
-#pragma unroll
-    for (int i = 0; i < C::DT; ++i) o[i] = zero_acc();
-    float m = -INFINITY, lsum = 0.f;
-
-    int kv_end = klen;
-    if (causal) kv_end = min(kv_end, q0 + C::QB);
-    const int ntiles = (kv_end + 63) / 64;
-
-    // pad columns: K's reduction pad must be zero (Q's is), V's pad only feeds discarded output rows but must not be NaN-free
-    // garbage either way -> zero both once (tile stores never touch them)
-    if (C::HDK != HD || C::VP > HD) {
-        for (int i = t; i < 2 * 64; i += C::NT2) {
-            if (C::HDK != HD) st16(sK + i * C::KP + HD, zero16());
-            for (int c = HD; c < C::VP; c += 8) st16(sV + i * C::VP + c, zero16());
-            if (C::ROWSUM_IN_MFMA) sV[i * C::VP + HD] = 0x3F80;  // bf16 1.0: the "ones" column
-        }
-    }
-    u32x4 rk[C::NCH], rv[C::NCH];
-    if (ntiles > 0) {
-        tile2_load<HD, NW>(rk, Kb, ldk, 0, S, t);
-        tile2_load<HD, NW>(rv, Vb, ldv, 0, S, t);
-        tile2_store<HD, NW, C::KP>(rk, sK, t);
-        tile2_store<HD, NW, C::VP>(rv, sV, t);
-        if (kmb && t < 64) {
-            const uint8_t mv = t < S ? kmb[t] : 0;
-            sM[t] = mv;
-            const unsigned long long all = ballot(mv != 0);
-            if (t == 0) sFlag[0] = int(all == ~0ull) | (int(all == 0ull) << 1);  // bit 0: every key of the tile valid, bit 1: none
-        }
-    }
-    for (int it = 0; it < ntiles; ++it) {
-        if (!(ARIA_ATTN_ABL & 64)) sync();  // tile `it` complete in buffer it&1; every wave is done reading the other buffer
-        const int cur = it & 1, kv0 = it * 64;
-        const bool more = it + 1 < ntiles && !(ARIA_ATTN_ABL & 32);
-        if (more) {
-            tile2_load<HD, NW>(rk, Kb, ldk, kv0 + 64, S, t);
-            tile2_load<HD, NW>(rv, Vb, ldv, kv0 + 64, S, t);
-        }
-        const bf16_t* cK = sK + cur * 64 * C::KP;
-        const bf16_t* cV = sV + cur * 64 * C::VP;
-        // (a tile without a single valid key -- the padded bottom rows of an image are one contiguous patch range -- contributes exactly
-        // nothing: every probability is exp2(-inf) = 0 and the running maximum does not move)
-        if (!(causal && kv0 > q_wmin + 31) && !(kmb && (sFlag[cur] & 2))) {  // wave-uniform: this wave has at least one visible key in the tile
-            f32x16 st[2];
-            st[0] = zero_acc();
-            st[1] = zero_acc();
-            if (ARIA_ATTN_ABL & 1) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st[i][r] = float((it * 7 + r * 3 + i + l) & 31) * 0.03125f;
-            } else {
-                // r04: the K fragments of k-step kk + 1 are requested before the two MFMAs of k-step kk are issued -- left to itself the
-                // scheduler sank every read to just in front of its MFMA (read, lgkmcnt(0), multiply: ten exposed LDS round trips per tile)
-                auto kf = [&](int i, int kk) __attribute__((always_inline)) -> s16x8 {
-                    return (ARIA_ATTN_ABL & 16) ? qf[(kk + i) % C::KS]
-                                                : *reinterpret_cast<const s16x8*>(cK + (i * 32 + (l & 31)) * C::KP + kk * 16 + h2 * 8);
-                };
-                s16x8 fr[2][2];
-                fr[0][0] = kf(0, 0);
-                fr[0][1] = kf(1, 0);
-#pragma unroll
-                for (int kk = 0; kk < C::KS; ++kk) {
-                    if (kk + 1 < C::KS) {
-                        fr[(kk + 1) & 1][0] = kf(0, kk + 1);
-                        fr[(kk + 1) & 1][1] = kf(1, kk + 1);
-                    }
-                    sched_fence();
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) st[i] = mfma32(fr[kk & 1][i], qf[kk], st[i]);
-                    sched_fence();
-                }
-            }
-            const bool need_mask = (kv0 + 64 > klen) || (causal && kv0 + 63 > q_wmin) || (kmb && !(sFlag[cur] & 1));
-            if (need_mask) {
-                const uint8_t* cM = sM + cur * 64;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int kvl = i * 32 + acc_row(r, l);
-                        const int kv = kv0 + kvl;
-                        bool dead = kv >= klen || (causal && kv > q_abs);
-                        if (kmb) dead = dead || !cM[kvl];
-                        if (dead) st[i][r] = -INFINITY;
-                    }
-            }
-            float mx = st[0][0];
-            if (!(ARIA_ATTN_ABL & 128)) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[i][r]);
-                mx = fmaxf(mx, shfl_xor(mx, 32));
-            } else {
-                mx = 8.f;
-            }
-            const float m_new = fmaxf(m, mx * scale2);
-            const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-            if (ballot(m_new > m) != 0ull) {  // wave-uniform lazy rescale: exact (alpha == 1 whenever it is skipped)
-                const float alpha = exp2_fast(m - m_safe);
-                if (!C::ROWSUM_IN_MFMA) lsum *= alpha;
-#pragma unroll
-                for (int i = 0; i < C::DT; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-                m = m_new;
-            }
-            float ps = 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 x = fma2(st[i][r], st[i][r + 1], scale2, -m_safe);
-#pragma unroll
-                    for (int z = 0; z < 2; ++z) {
-                        const float p = (ARIA_ATTN_ABL & 2) ? x[z] : exp2_fast(x[z]);
-                        st[i][r + z] = p;
-                        if (!C::ROWSUM_IN_MFMA) ps += p;
-                    }
-                }
-            if (!C::ROWSUM_IN_MFMA) lsum += ps;
-            // O^T += V^T P^T
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const s16x8 pf = pack_frag(st[i], u);
-                    if (ARIA_ATTN_ABL & 4) {
-                        abl_keep(pf);
-                        continue;
-                    }
-                    const bf16_t* vrow = cV + (i * 32 + 16 * u + 4 * h2 + ((l & 15) >> 2)) * C::VP + 16 * ((l >> 4) & 1) + 4 * (l & 3);
-#pragma unroll
-                    for (int dt = 0; dt < C::DT; ++dt) {
-                        s16x8 vf;
-                        if (ARIA_ATTN_ABL & 8) {
-                            vf = qf[dt];
-                        } else {
-                            const s16x4 a0 = ds_read_tr16(vrow + 32 * dt);
-                            const s16x4 a1 = ds_read_tr16(vrow + 8 * C::VP + 32 * dt);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                vf[e] = a0[e];
-                                vf[4 + e] = a1[e];
-                            }
-                        }
-                        o[dt] = mfma32(vf, pf, o[dt]);
-                    }
-                }
-        }
-        if (more) {  // stage tile it+1 into the other buffer (nobody reads it before the next barrier)
-            const int nb = cur ^ 1, kvn = kv0 + 64;
-            tile2_store<HD, NW, C::KP>(rk, sK + nb * 64 * C::KP, t);
-            tile2_store<HD, NW, C::VP>(rv, sV + nb * 64 * C::VP, t);
-            if (kmb && t < 64) {
-                const uint8_t mv = (kvn + t < S) ? kmb[kvn + t] : 0;
-                sM[nb * 64 + t] = mv;
-                const unsigned long long all = ballot(mv != 0);
-                if (t == 0) sFlag[nb] = int(all == ~0ull) | (int(all == 0ull) << 1);
-            }
-        }
-    }
-    // ROWSUM_IN_MFMA: feature row HD = 32 (DT-1) + 8 sits in accumulator register 4 of the lanes with h2 == 0
-    const float ltot = C::ROWSUM_IN_MFMA ? shfl(o[C::DT - 1][4], l & 31) : lsum + shfl_xor(lsum, 32);
-    const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
-    if (q_abs < Sq) {
-        if (h2 == 0 && LSE)
-            LSE[((long long)b * H + head) * Sq + q_abs] = (ltot > 0.f) ? (m + log2f(ltot)) * 0.6931471805599453f : -INFINITY;
-        bf16_t* orow = O + (tokq0 + q_abs) * ldo + head * HD;
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int d0 = 32 * dt + 8 * rg + 4 * h2;
-                if (d0 < HD) {
-                    u32x2 v;
-                    v[0] = pack2bf(o[dt][4 * rg] * inv, o[dt][4 * rg + 1] * inv);
-                    v[1] = pack2bf(o[dt][4 * rg + 2] * inv, o[dt][4 * rg + 3] * inv);
-                    *reinterpret_cast<u32x2*>(orow + d0) = v;
-                }
-            }
-    }
-}
+// The kernel text lives in attn_fwd2_kernel.h and is compiled twice: as attn_fwd2_kernel (rows and causal positions coincide) and as
+// attn_fwd2_off_kernel (prefill at a cache offset: query row i sits at position q_off + i).  Textual inclusion, not a shared __device__ body:
+// one more level of inlining reorders the existing kernels' code (compared with hipcc -S), and their wait placement is guarded by tests.
+#define ATTN_FWD_OFFSET 0
+#include "attn_fwd2_kernel.h"
+#undef ATTN_FWD_OFFSET
+#define ATTN_FWD_OFFSET 1
+#include "attn_fwd2_kernel.h"
+#undef ATTN_FWD_OFFSET
 
 // =========================================================================================== delta = rowsum(O * dO)
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* O, const bf16_t* dO, float* delta, int S, int H, int HD,
@@ -1398,145 +1188,13 @@ __device__ __forceinline__ void fwd3_step(f32x16 (&st)[2], f32x16 (&sn)[2], f32x
 // 145 VGPRs, THREE waves per SIMD).  Measured for the ViT's shape (profiles/r04_attn_fwd3_ab.json): the third wave is worth more than the
 // in-wave overlap, and with it LDS-DMA staging into the conflict-free images (SQ_LDS_BANK_CONFLICT 0, was 8 % of the LDS cycles) is level
 // with v2's register staging -- so hd 72 stays on v2 by default and both v3 forms are kept selectable (ARIA_ATTN_FWD) as measurements.
-template <int HD, int NW, bool PIPE>
-__global__ __launch_bounds__(NW * 64) void attn_fwd3_kernel(const bf16_t* Q, const bf16_t* K, const bf16_t* V, bf16_t* O, float* LSE,
-                                                        const int32_t* kv_len, const uint8_t* key_mask, int Sq, int S, int H,
-                                                        long long ldq, long long ldk, long long ldv, long long ldo, float scale,
-                                                        int causal, int nbatch) {
-    using F = FwdFmt<HD>;
-    using L = Fwd3Smem<HD>;
-    constexpr int KS = F::KS, DT = F::DT;
-    ARIA_DYN_SMEM(smem);
-    char* sK = smem + L::K0;
-    char* sV = smem + L::V0;
-    uint8_t* sM = reinterpret_cast<uint8_t*>(smem + L::M0);   // [3][64]: the key-mask bytes of tiles t, t + 1, t + 2
-    int* sFlag = reinterpret_cast<int*>(smem + L::FLAG0);     // [3]: bit 0 every key of the tile valid, bit 1 none
-    const int t = threadIdx.x, l = t & 63, w = first_lane(t >> 6), h2 = l >> 5;
-    int qblk, head, b;
-    constexpr int QB = NW * 32, KA = PIPE ? 1 : 0;  // queries per workgroup; how many tiles K runs ahead of V in LDS
-    static_assert(HD != 128 || NW == 8, "tile_dma3 deals a tile's 16 pieces to 8 waves");
-    if (!attn_block_coords((Sq + QB - 1) / QB, H, nbatch, causal, true, qblk, head, b)) return;
-    const int q0 = qblk * QB;
-    const long long tok0 = (long long)b * S, tokq0 = (long long)b * Sq;
-    const bf16_t* Qb = Q + tokq0 * ldq + head * HD;
-    const bf16_t* Kb = K + tok0 * ldk + head * HD;
-    const bf16_t* Vb = V + tok0 * ldv + head * HD;
-    const uint8_t* kmb = key_mask ? key_mask + tok0 : nullptr;
-    const int q_wmin = q0 + 32 * w, q_abs = q_wmin + (l & 31);
-    const int klen = kv_len ? min(S, kv_len[b]) : S;
-    const float scale2 = scale * 1.4426950408889634f;
-    F fmt;
-    fmt.init(w, l, NW);
-
-    s16x8 qf[KS];
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-        u32x4 v = zero16();
-        const int col = kk * 16 + h2 * 8;
-        if (q_abs < Sq && col < HD) v = ld16(Qb + (long long)q_abs * ldq + col);
-        qf[kk] = __builtin_bit_cast(s16x8, v);
-    }
-    f32x16 o[DT];
-#pragma unroll
-    for (int i = 0; i < DT; ++i) o[i] = zero_acc();
-    float m = -INFINITY, lsum = 0.f;
-    int kv_end = klen;
-    if (causal) kv_end = min(kv_end, q0 + QB);
-    const int ntiles = (kv_end + 63) / 64;
-
-    // key-mask bytes of one tile -> ring slot tile % 3 (threads 0..63: wave 0)
-    auto mask_fetch = [&](int tile) __attribute__((always_inline)) -> uint8_t { return (tile * 64 + t < S) ? kmb[tile * 64 + t] : uint8_t(0); };
-    auto mask_park = [&](int tile, uint8_t mv) __attribute__((always_inline)) {
-        sM[(tile % 3) * 64 + t] = mv;
-        const unsigned long long all = ballot(mv != 0);
-        if (t == 0) sFlag[tile % 3] = int(all == ~0ull) | (int(all == 0ull) << 1);
-    };
-    if (ntiles > 0) {
-        if (HD == 72) {  // what the pad-column reads behind the last rows touch must hold finite values (0 x NaN = NaN)
-            if (t < 2) st16(sK + t * F::KTILE + F::KTILE - 16, zero16());
-            if (t >= 64 && t < 68) st16(sV + ((t - 64) >> 1) * F::VTILE + F::VTILE - 32 + 16 * (t & 1), zero16());
-        }
-        fmt.dma_k(Kb, ldk, 0, S - 1, sK, w, l);
-        fmt.dma_v(Vb, ldv, 0, S - 1, sV, w, l);
-        if (PIPE && ntiles > 1) fmt.dma_k(Kb, ldk, 64, S - 1, sK + F::KTILE, w, l);
-        if (kmb && t < 64) {
-            mask_park(0, mask_fetch(0));
-            if (ntiles > 1) mask_park(1, mask_fetch(1));
-        }
-    }
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) settle(qf[kk]);
-    // tiles this wave works on: the causal diagonal ends its run early (the workgroup's later tiles hold no key it may see); a tile
-    // WITHOUT a valid key (padded image rows) is worked on like any other -- every probability is exp2(-inf) = 0 and the running maximum
-    // does not move, so it contributes exactly nothing (v2 skipped it; same bits)
-    const int nmine = causal ? min(ntiles, (q_wmin + 31) / 64 + 1) : ntiles;
-    auto tile_masked = [&](int tile) __attribute__((always_inline)) -> bool {
-        return (tile * 64 + 64 > klen) || (causal && tile * 64 + 63 > q_wmin) || (kmb && !(sFlag[tile % 3] & 1));
-    };
-    // the part of an iteration every wave owes the workgroup: the tile barrier, its DMA pieces of K(it + 2) / V(it + 1), the mask bytes
-    uint8_t mv = 0;
-    auto duties = [&](int it) __attribute__((always_inline)) {
-        wait_vm<0>();  // this wave's pieces of K(it + KA) and V(it) have landed
-        sync();        // ... everybody's; every wave is done with K(it + KA - 1) and V(it - 1)
-        if (it + KA + 1 < ntiles) fmt.dma_k(Kb, ldk, (it + KA + 1) * 64, S - 1, sK + ((it + KA + 1) & 1) * F::KTILE, w, l);
-        if (it + 1 < ntiles) fmt.dma_v(Vb, ldv, (it + 1) * 64, S - 1, sV + ((it + 1) & 1) * F::VTILE, w, l);
-        if (kmb && t < 64 && it + 2 < ntiles) mv = mask_fetch(it + 2);
-    };
-    auto park = [&](int it) __attribute__((always_inline)) {
-        if (kmb && t < 64 && it + 2 < ntiles) mask_park(it + 2, mv);
-    };
-    f32x16 sa[2], sb[2];
-    if (PIPE && ntiles > 0) {
-        wait_vm<0>();
-        sync();
-        if (nmine > 0) fwd3_qk<HD>(sa, sK, qf, l);
-    }
-    // one iteration: tile `it` (PIPE: its scores are in `cur`) -> softmax + P V; PIPE: tile it + 1 -> scores into `nxt`
-    auto iterate = [&](int it, f32x16 (&cur)[2], f32x16 (&nxt)[2]) __attribute__((always_inline)) {
-        duties(it);
-        if (!PIPE) fwd3_qk<HD>(cur, sK + (it & 1) * F::KTILE, qf, l);
-        if (tile_masked(it)) fwd3_mask(cur, sM + (it % 3) * 64, kmb != nullptr, it * 64, klen, causal, q_abs, l);
-        fwd3_step<HD, PIPE>(cur, nxt, o, m, lsum, qf, sV + (it & 1) * F::VTILE, sK + ((it + 1) & 1) * F::KTILE, scale2, l);
-        park(it);
-    };
-    int it = 0;
-    if (PIPE) {
-        for (; it + 1 < nmine; it += 2) {
-            iterate(it, sa, sb);
-            iterate(it + 1, sb, sa);
-        }
-        if (it < nmine) {
-            iterate(it, sa, sb);
-            ++it;
-        }
-    } else {
-        for (; it < nmine; ++it) iterate(it, sa, sb);
-    }
-    for (; it < ntiles; ++it) {  // the workgroup's remaining tiles (other waves' diagonals): barriers and staging only
-        duties(it);
-        park(it);
-    }
-    // ROWSUM_IN_MFMA: feature row HD = 32 (DT-1) + 8 sits in accumulator register 4 of the lanes with h2 == 0
-    const float ltot = F::ROWSUM_IN_MFMA ? shfl(o[DT - 1][4], l & 31) : lsum + shfl_xor(lsum, 32);
-    const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
-    if (q_abs < Sq) {
-        if (h2 == 0 && LSE)
-            LSE[((long long)b * H + head) * Sq + q_abs] = (ltot > 0.f) ? (m + log2f(ltot)) * 0.6931471805599453f : -INFINITY;
-        bf16_t* orow = O + (tokq0 + q_abs) * ldo + head * HD;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int d0 = 32 * dt + 8 * rg + 4 * h2;
-                if (d0 < HD) {
-                    u32x2 v;
-                    v[0] = pack2bf(o[dt][4 * rg] * inv, o[dt][4 * rg + 1] * inv);
-                    v[1] = pack2bf(o[dt][4 * rg + 2] * inv, o[dt][4 * rg + 3] * inv);
-                    *reinterpret_cast<u32x2*>(orow + d0) = v;
-                }
-            }
-    }
-}
+// (kernel text in attn_fwd3_kernel.h, compiled twice like attn_fwd2_kernel.h: attn_fwd3_kernel and attn_fwd3_off_kernel)
+#define ATTN_FWD_OFFSET 0
+#include "attn_fwd3_kernel.h"
+#undef ATTN_FWD_OFFSET
+#define ATTN_FWD_OFFSET 1
+#include "attn_fwd3_kernel.h"
+#undef ATTN_FWD_OFFSET
 
 
 thread_local int g_last_fwd_variant = 0;  // 2: attn_fwd2 (staged through registers), 3: attn_fwd3 (software-pipelined, LDS-DMA)
@@ -1552,7 +1210,7 @@ int aria_attn_fwd(const void* q, const void* k, const void* v, void* o, float* l
                   float scale, int causal, void* stream) {
     if (!q || !k || !v || !o || B < 0 || Sq < 0 || Skv < 0 || H <= 0) return ARIA_ERR_INVALID;
     if (hd != 64 && hd != 72 && hd != 128) return ARIA_ERR_UNSUPPORTED;
-    if (causal && Sq != Skv) return ARIA_ERR_UNSUPPORTED;
+    if (causal && Sq != Skv) return ARIA_ERR_UNSUPPORTED;   // (new queries behind a cached prefix: aria_attn_fwd_offset)
     if (!al16(q) || !al16(k) || !al16(v) || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || (reinterpret_cast<uintptr_t>(o) & 7))
         return ARIA_ERR_ALIGN;
     if (B == 0 || Sq == 0) return ARIA_OK;
@@ -1587,6 +1245,37 @@ int aria_attn_fwd(const void* q, const void* k, const void* v, void* o, float* l
         ARIA_LAUNCH((attn_fwd2_kernel<64, 8>), dim3(attn_grid((Sq + 255) / 256, H, B)), dim3(512), size_t(Cfg2<64>::SMEM), stream, Q, K, V,
                     static_cast<bf16_t*>(o), lse, kv_len, key_mask, int(Sq), int(Skv), int(H), (long long)ldq, (long long)ldk,
                     (long long)ldv, (long long)ldo, scale, causal, int(B));
+    return aria_check_launch();
+}
+
+int aria_attn_fwd_offset(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* kv_len, const uint8_t* key_mask,
+                         int64_t B, int64_t Sq, int64_t Skv, int64_t q_off, int64_t H, int64_t hd, int64_t ldq, int64_t ldk, int64_t ldv,
+                         int64_t ldo, float scale, void* stream) {
+    if (!q || !k || !v || !o || B < 0 || Sq < 0 || Skv < 0 || H <= 0) return ARIA_ERR_INVALID;
+    if (q_off < 0 || q_off + Sq > Skv || Skv > 0x7fffffff) return ARIA_ERR_INVALID;
+    if (hd != 64 && hd != 128) return ARIA_ERR_UNSUPPORTED;   // (hd 72 is the ViT: never causal)
+    if (!al16(q) || !al16(k) || !al16(v) || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || (reinterpret_cast<uintptr_t>(o) & 7))
+        return ARIA_ERR_ALIGN;
+    if (B == 0 || Sq == 0) return ARIA_OK;
+    const bf16_t *Q = static_cast<const bf16_t*>(q), *K = static_cast<const bf16_t*>(k), *V = static_cast<const bf16_t*>(v);
+    const char* fwdv = std::getenv("ARIA_ATTN_FWD");             // "2": the register-staged family for hd 128 too (as in aria_attn_fwd)
+    const char* grp = std::getenv("ARIA_ATTN_CAUSAL_GROUPED");   // "1" / "0": force the XCD-grouped causal block order on / off
+    const int causal_arg = (grp ? grp[0] == '1' : Sq >= 32768) ? 2 : 1;
+    const bool v3 = !(fwdv && fwdv[0] == '2') && hd == 128;
+    g_last_fwd_variant = v3 ? 3 : 2;
+    const dim3 grid(attn_grid((Sq + 255) / 256, H, B));
+    if (v3)
+        ARIA_LAUNCH((attn_fwd3_off_kernel<128, 8, true>), grid, dim3(512), size_t(Fwd3Smem<128>::BYTES), stream, Q, K, V,
+                    static_cast<bf16_t*>(o), lse, kv_len, key_mask, int(Sq), int(Skv), int(H), (long long)ldq, (long long)ldk,
+                    (long long)ldv, (long long)ldo, scale, causal_arg, int(B), int(q_off));
+    else if (hd == 128)
+        ARIA_LAUNCH((attn_fwd2_off_kernel<128, 8>), grid, dim3(512), size_t(Cfg2<128>::SMEM), stream, Q, K, V,
+                    static_cast<bf16_t*>(o), lse, kv_len, key_mask, int(Sq), int(Skv), int(H), (long long)ldq, (long long)ldk,
+                    (long long)ldv, (long long)ldo, scale, causal_arg, int(B), int(q_off));
+    else
+        ARIA_LAUNCH((attn_fwd2_off_kernel<64, 8>), grid, dim3(512), size_t(Cfg2<64>::SMEM), stream, Q, K, V,
+                    static_cast<bf16_t*>(o), lse, kv_len, key_mask, int(Sq), int(Skv), int(H), (long long)ldq, (long long)ldk,
+                    (long long)ldv, (long long)ldo, scale, causal_arg, int(B), int(q_off));
     return aria_check_launch();
 }
 

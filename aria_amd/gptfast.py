@@ -126,9 +126,11 @@ class Attention(nn.Module):
         self.kv_cache: Optional[KVCache] = None
         self.hdp = Fn._pad_hd(config.head_dim, need_bwd=False)  # kernels are native for 64 / 72 / 128
 
-    def forward(self, x2d, B, S, freqs_cis, pos32, kv_len, prefill: bool, pos_is_arange: bool = False):
+    def forward(self, x2d, B, S, freqs_cis, pos32, kv_len, prefill: bool, pos_is_arange: bool = False, q_offset: Optional[int] = None):
         c = self.config
         D, H, hd, hdp = c.dim, c.n_head, c.head_dim, self.hdp
+        if q_offset is not None:
+            return self._forward_continuation(x2d, B, S, freqs_cis, pos32, q_offset)
         if (prefill and self.kv_cache is not None and B == 1 and hdp == hd and x2d.shape[0] == S and S <= self.kv_cache.k.shape[1]
                 and pos_is_arange and ops.qkv_rope_cache_fusable(D, x2d.shape[1], hd)):
             # K7: projection + interleaved RoPE + KVCache.update (model.py:423-435, 67-93) as ONE launch -- q to its own buffer, rotated k and v
@@ -160,6 +162,37 @@ class Attention(nn.Module):
             cache.v.view(-1, Dp).index_copy_(0, rows, v)
             o, _ = ops.attention_fwd(q, cache.k.view(-1, Dp), cache.v.view(-1, Dp), B, 1, H, hdp, hd ** -0.5, False,
                                      kv_len=kv_len, Skv=Smax)
+        if hdp != hd:
+            o = Fn._unpad_heads(o, H, hd, hdp).contiguous()
+        return ops.gemm(o, self.wo.weight)
+
+    def _forward_continuation(self, x2d, B, S, freqs_cis, pos32, p0: int):
+        """Prefill at a cache offset (chunked prefill, chat prefix reuse): the S tokens sit at positions p0 .. p0+S-1 (Transformer.forward
+        checked that on the host), cache rows 0 .. p0-1 hold the prefix.  What the reference does with KVCache.update indexed by input_pos
+        and the mask rows causal_mask[input_pos] over the whole cache (gptfast/model.py:76-91, 199-231): the new k / v rows go to cache rows
+        p0.., and the attention kernel reads the cache in place with the queries' causal position shifted by p0 (aria_attn_fwd_offset)."""
+        c = self.config
+        D, H, hd, hdp = c.dim, c.n_head, c.head_dim, self.hdp
+        cache = self.kv_cache
+        Smax = cache.k.shape[1]
+        if B == 1 and hdp == hd and x2d.shape[0] == S and ops.qkv_rope_cache_fusable(D, x2d.shape[1], hd):
+            # K7 with explicit positions: rotation and cache row both come from pos32 (= p0 + arange(S), host-checked)
+            q = ops.gemm_qkv_rope_cache(x2d, self.wqkv.weight, freqs_cis, pos32, cache.k, cache.v, S, hd)
+        else:
+            qkv = ops.gemm(x2d, self.wqkv.weight)
+            ops.rope_interleaved_(qkv[:, :2 * D], freqs_cis, 2 * H, hd, pos32)
+            q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
+            if hdp != hd:  # toy head dims only (tests)
+                q, k, v = (Fn._pad_heads(t, H, hd, hdp) for t in (q, k, v))
+            cache.k[:B, p0:p0 + S].copy_(k.reshape(B, S, H * hdp))
+            cache.v[:B, p0:p0 + S].copy_(v.reshape(B, S, H * hdp))
+        Dp = H * hdp
+        if B == 1:
+            o, _ = ops.attention_fwd(q, cache.k[0, :p0 + S], cache.v[0, :p0 + S], 1, S, H, hdp, hd ** -0.5, True, Skv=p0 + S, q_offset=p0)
+        else:  # every batch entry's rows lie Smax apart: the whole cache is the operand, the live length rides in kv_len
+            kv_len = torch.full((B,), p0 + S, dtype=torch.int32, device=x2d.device)
+            o, _ = ops.attention_fwd(q, cache.k.view(-1, Dp), cache.v.view(-1, Dp), B, S, H, hdp, hd ** -0.5, True, kv_len=kv_len, Skv=Smax,
+                                     q_offset=p0)
         if hdp != hd:
             o = Fn._unpad_heads(o, H, hd, hdp).contiguous()
         return ops.gemm(o, self.wo.weight)
@@ -224,7 +257,7 @@ class TransformerBlock(nn.Module):
         self.ffn_norm = RMSNorm(config.dim, config.norm_eps)
         self.attention_norm = RMSNorm(config.dim, config.norm_eps)
 
-    def forward(self, res, delta, B, S, freqs_cis, pos32, kv_len, prefill, pos_is_arange=False):
+    def forward(self, res, delta, B, S, freqs_cis, pos32, kv_len, prefill, pos_is_arange=False, q_offset=None):
         """gptfast/model.py:236-260 with the two residual adds folded into the norm that follows each (``rmsnorm`` with a residual: the
         sum is rounded to bf16 and written once, then normalised -- the same bits as ``add`` followed by ``rmsnorm``, two launches and two
         passes over [T, D] less per layer).  The block's input is ``res + delta`` (``delta`` None for the first block); it returns
@@ -233,7 +266,7 @@ class TransformerBlock(nn.Module):
             x, xn = res, self.attention_norm(res)
         else:
             xn, x, _ = ops.rmsnorm(delta, self.attention_norm.weight, self.attention_norm.eps, residual=res, want_rstd=False)
-        a = self.attention(xn, B, S, freqs_cis, pos32, kv_len, prefill, pos_is_arange)
+        a = self.attention(xn, B, S, freqs_cis, pos32, kv_len, prefill, pos_is_arange, q_offset)
         hn, h, _ = ops.rmsnorm(a, self.ffn_norm.weight, self.ffn_norm.eps, residual=x, want_rstd=False)
         return h, self.feed_forward(hn)
 
@@ -304,7 +337,8 @@ class Transformer(nn.Module):
 
     def forward(self, idx: Optional[torch.Tensor], input_pos: Optional[torch.Tensor] = None,
                 input_embeds: Optional[torch.Tensor] = None, last_only: bool = False) -> torch.Tensor:
-        """idx [B,S]; input_pos [S] (prefill, = arange) or [1] / [B] device tensor (decode cursor).  -> logits [B,S,V]."""
+        """idx [B,S]; input_pos [S] (prefill: arange(S), or p0 + arange(S) to continue behind p0 cached positions) or [1] / [B] device
+        tensor (decode cursor).  -> logits [B,S,V]."""
         x = self.tok_embeddings(idx) if input_embeds is None else input_embeds
         B, S, D = x.shape
         x2d = x.reshape(B * S, D).contiguous()
@@ -312,13 +346,27 @@ class Transformer(nn.Module):
         if not prefill and B == 1 and self.use_decode_engine and self._engine_ok():
             return self._engine.step(x, input_pos)
         pos_is_arange = input_pos is None
+        q_offset = None   # p0 of a prefill that continues behind p0 cached positions
         if input_pos is None:
             input_pos = torch.arange(S, device=x.device)
         elif prefill and input_pos.numel() == S:
             # the prefill contract is input_pos = arange(S) (gptfast/generate.py:147-150; KVCache.update writes rows 0..S-1): checked here, once
             # per prefill call (a host read of S integers), so that the fused projection + RoPE + cache-write launch may take the position
             # from the row index instead of trusting a device tensor
-            pos_is_arange = bool(torch.equal(input_pos.reshape(-1).long().cpu(), torch.arange(S)))
+            # p0 + arange(S), p0 > 0: prefill at a cache offset (the prefix's rows are resident).  Any other position list is refused: no
+            # launch here serves scattered prefill positions, and writing rows 0..S-1 regardless was silently wrong.
+            host_pos = input_pos.reshape(-1).long().cpu()
+            p0 = int(host_pos[0])
+            if not torch.equal(host_pos, p0 + torch.arange(S)) or p0 < 0:
+                raise ValueError(f"Transformer.forward: a prefill's input_pos must be p0 + arange({S}); got {host_pos.tolist()[:8]}...")
+            pos_is_arange = p0 == 0
+            if p0 > 0:
+                q_offset = p0
+                if self.layers[0].attention.kv_cache is None:
+                    raise ValueError("Transformer.forward: a prefill at position p0 > 0 needs setup_caches() and the prefix in the cache")
+                if B > self.max_batch_size or p0 + S > self.max_seq_length:
+                    raise ValueError(f"Transformer.forward: positions {p0}..{p0 + S - 1} of {B} sequences do not fit the caches "
+                                     f"({self.max_batch_size} x {self.max_seq_length}): setup_caches() first")
         if prefill:
             pos32 = input_pos.to(torch.int32).reshape(1, S).expand(B, S).reshape(-1).contiguous()
             kv_len = None
@@ -327,16 +375,16 @@ class Transformer(nn.Module):
             kv_len = pos32 + 1
         res, delta = x2d, None
         if self._w8:
-            return self._forward_w8(res, B, S, pos32, kv_len, prefill, pos_is_arange, last_only)
+            return self._forward_w8(res, B, S, pos32, kv_len, prefill, pos_is_arange, last_only, q_offset)
         for layer in self.layers:
-            res, delta = layer(res, delta, B, S, self.freqs_cis, pos32, kv_len, prefill, pos_is_arange)
+            res, delta = layer(res, delta, B, S, self.freqs_cis, pos32, kv_len, prefill, pos_is_arange, q_offset)
         h = ops.rmsnorm(delta, self.norm.weight, self.norm.eps, residual=res, want_rstd=False)[0] if delta is not None else self.norm(res)
         if last_only:
             h = h.view(B, S, D)[:, -1].contiguous()
             return ops.gemm(h, self.output.weight).view(B, 1, -1)
         return ops.gemm(h, self.output.weight).view(B, S, -1)
 
-    def _forward_w8(self, res, B, S, pos32, kv_len, prefill, pos_is_arange, last_only):
+    def _forward_w8(self, res, B, S, pos32, kv_len, prefill, pos_is_arange, last_only, q_offset=None):
         """Every forward of an int8 model that the int8 engine does not take (prefill, B > 1, ``use_decode_engine = False``, shapes the
         engine declines): before a layer runs, its codes are expanded into ONE bf16 scratch sized for a layer (quantize.dequantized_layer)
         and the bf16 tile kernels run on views of it.  A correctness path, not a fast one: a B > 1 decode step pays a full dequant of every
@@ -345,7 +393,7 @@ class Transformer(nn.Module):
         delta = None
         for layer in self.layers:
             with quantize.dequantized_layer(self, layer):
-                res, delta = layer(res, delta, B, S, self.freqs_cis, pos32, kv_len, prefill, pos_is_arange)
+                res, delta = layer(res, delta, B, S, self.freqs_cis, pos32, kv_len, prefill, pos_is_arange, q_offset)
         h = ops.rmsnorm(delta, self.norm.weight, self.norm.eps, residual=res, want_rstd=False)[0]
         if last_only:
             return quantize.head_logits(self, h.view(B, S, D)[:, -1].contiguous(), True).view(B, 1, -1)
@@ -589,22 +637,41 @@ def _dbg(msg):
 def generate(model: Aria, input_ids: torch.Tensor, max_new_tokens: int, *, pixel_values=None, pixel_mask=None,
              temperature: float = 0.8, top_k: Optional[int] = 200, decoder: Optional[DecodeGraph] = None,
              stop_token: Optional[int] = None, use_graph: bool = False, callback=None,
-             cache_size: Optional[int] = None) -> Tuple[torch.Tensor, Optional[DecodeGraph]]:
+             cache_size: Optional[int] = None, prefill_chunk: Optional[int] = None,
+             cached_prefix: int = 0) -> Tuple[torch.Tensor, Optional[DecodeGraph]]:
     """gptfast/generate.py:112-177: prefill (ViT + projector + full prompt) then token-by-token decode.  ``callback(new_tokens)`` is the
     reference's early-stop hook (decode_n_tokens :80-105: called after every token with the list of new token tensors, ``True`` stops);
-    ``stop_token`` is the cheap form of the same for single-token stop strings.  ``cache_size`` pre-sizes the static KV cache (:139-150)."""
+    ``stop_token`` is the cheap form of the same for single-token stop strings.  ``cache_size`` pre-sizes the static KV cache (:139-150).
+    ``cached_prefix`` = P: rows 0..P-1 of the KV cache already hold ``input_ids[:, :P]`` (an earlier call on this model left them there), so
+    only the suffix is embedded and prefilled -- ``pixel_values`` / ``pixel_mask`` are then the images whose placeholders lie in the suffix.
+    ``prefill_chunk``: the tokens to prefill run in pieces of at most that many (peak activation memory follows the piece, not the prompt);
+    every piece behind the first is a prefill at a cache offset (Transformer.forward with input_pos = p0 + arange)."""
     T = input_ids.size(1)
     dev = input_ids.device
+    P = int(cached_prefix)
+    if not 0 <= P <= max(T - 1, 0):
+        raise ValueError(f"cached_prefix must lie in 0..{T - 1} (at least the last prompt token is prefilled); got {P}")
+    if prefill_chunk is not None and prefill_chunk < 1:
+        raise ValueError("prefill_chunk must be a positive number of tokens")
     if cache_size is not None and cache_size < T + max_new_tokens:
         raise ValueError("need cache_size to be greater than max_new_tokens + size-of-prompt")
     if model.llm.max_seq_length < max(T + max_new_tokens, cache_size or 0):
+        if P > 0:
+            raise ValueError(f"cached_prefix={P}: the KV cache ({model.llm.max_seq_length} positions) would have to be re-allocated for "
+                             f"{max(T + max_new_tokens, cache_size or 0)}, which drops the prefix -- size the cache before the first call")
         model.setup_caches(1, max(T + max_new_tokens, cache_size or 0))
         decoder = None
     _dbg("start")
-    emb = model.prepare_embeddings(input_ids, pixel_values, pixel_mask)
+    emb = model.prepare_embeddings(input_ids[:, P:] if P else input_ids, pixel_values, pixel_mask)
     _dbg("emb")
-    input_pos = torch.arange(0, T, device=dev)
-    logits = model(None, input_pos, emb, last_only=True)
+    chunk = T - P if prefill_chunk is None else min(prefill_chunk, T - P)
+    if P == 0 and chunk == T:
+        input_pos = torch.arange(0, T, device=dev)
+        logits = model(None, input_pos, emb, last_only=True)
+    else:
+        for s in range(P, T, chunk):   # (a one-token piece is a decode step at its position; only the last piece's logits are used)
+            e = min(T, s + chunk)
+            logits = model(None, torch.arange(s, e, device=dev), emb[:, s - P:e - P], last_only=True)
     _dbg("prefill")
     nxt, _ = sample(logits, temperature, top_k)
     _dbg("sample")

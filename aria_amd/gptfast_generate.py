@@ -16,9 +16,13 @@ from . import gptfast as G
 
 class GenerationConfig:
     def __init__(self, max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8, cache_size: Optional[int] = None,
-                 linear_causal_mask: bool = False, stop_strings: Optional[List[str]] = None):
+                 linear_causal_mask: bool = False, stop_strings: Optional[List[str]] = None, prefill_chunk: Optional[int] = None,
+                 reuse_prefix: bool = False):
+        """``prefill_chunk``: prefill the prompt in pieces of at most that many tokens.  ``reuse_prefix``: a ``Generator`` keeps what its last
+        call left in the KV cache and prefills only what the next prompt adds behind the common prefix (multi-turn chat)."""
         self.max_new_tokens, self.top_k, self.temperature = max_new_tokens, top_k, temperature
         self.cache_size, self.linear_causal_mask, self.stop_strings = cache_size, linear_causal_mask, stop_strings
+        self.prefill_chunk, self.reuse_prefix = prefill_chunk, reuse_prefix
 
 
 class ModelConfig:
@@ -55,13 +59,35 @@ def load_model_and_processor(checkpoint_path: Path, device, precision=torch.bflo
     return model.eval(), processor
 
 
+def reusable_prefix(old_ids: List[int], new_ids: List[int], image_token_index: int, old_images_match: bool) -> int:
+    """How many leading tokens of ``new_ids`` need no prefill when the KV cache holds ``old_ids`` (rows 0..len(old_ids)-1).
+    L = the longest common prefix, capped at len(new_ids) - 1 (the last prompt token is always run: its logits are the first sample).
+    If that prefix covers EVERY image placeholder of ``old_ids`` and ``old_images_match`` (the old call's pixel values and masks equal
+    the leading ones of the new call), all of it is kept, and only the new call's further images go through the ViT.  Otherwise the cut
+    falls in front of the first image placeholder: a run of placeholders is filled from the projector's output in order, so a suffix
+    must hold whole images, and with different pixels the cached rows of the placeholders are stale."""
+    L, cap = 0, min(len(old_ids), len(new_ids) - 1)
+    while L < cap and old_ids[L] == new_ids[L]:
+        L += 1
+    n_img_old = sum(1 for t in old_ids if t == image_token_index)
+    if old_images_match and sum(1 for t in new_ids[:L] if t == image_token_index) == n_img_old:
+        return L
+    first_img = next((i for i, t in enumerate(new_ids) if t == image_token_index), len(new_ids))
+    return min(L, first_img)
+
+
 class Generator:
-    """generate.py:281-346.  ``Generator(model_config, generation_config).generate(messages, image, detokenize=True)``."""
+    """generate.py:281-346.  ``Generator(model_config, generation_config).generate(messages, image, detokenize=True)``.
+    With ``generation_config.reuse_prefix`` it remembers the token ids resident in the KV cache after a call (the prompt and every generated
+    token that was fed back, i.e. all but the last sampled one) and that call's pixel values / masks; the next call prefills only the
+    tokens behind ``reusable_prefix``.  ``last_prefill_tokens``: how many prompt tokens the last call prefilled."""
 
     def __init__(self, model_config: ModelConfig, generation_config: GenerationConfig, model: Optional[G.Aria] = None, processor=None):
         self.model_config, self.generation_config = model_config, generation_config
         self.model, self.processor = model, processor
         self._decoder = None
+        self._resident = None            # (ids, pixel_values, pixel_mask) of what the KV cache holds (reuse_prefix)
+        self.last_prefill_tokens = 0
         if self.model is None:
             self.model, self.processor = load_model_and_processor(model_config.checkpoint_path, model_config.device, model_config.precision,
                                                                   getattr(model_config, "model_args", None), processor=processor,
@@ -74,6 +100,22 @@ class Generator:
             ids = tok.encode(s)
             (single if len(ids) == 1 else multi).append(ids[0] if len(ids) == 1 else s)
         return single, multi
+
+    def _cached_prefix(self, resident, ids, pv, pm):
+        """-> (P, n_old): the reusable prefix of this call against what the cache holds, and how many leading images the ViT may skip."""
+        gc = self.generation_config
+        old_ids, old_pv, old_pm = resident
+        T = ids.shape[1]
+        if self.model.llm.max_seq_length < max(T + gc.max_new_tokens, gc.cache_size or 0):
+            return 0, 0   # generate() will re-allocate the cache: nothing survives
+        n_old = 0 if old_pv is None else old_pv.shape[0]
+        match = n_old == 0 or (pv is not None and pv.shape[0] >= n_old and pv.shape[1:] == old_pv.shape[1:] and torch.equal(pv[:n_old], old_pv)
+                               and ((pm is None and old_pm is None) or (pm is not None and old_pm is not None and pm.shape[1:] == old_pm.shape[1:]
+                                                                        and torch.equal(pm[:n_old], old_pm))))
+        new_ids, img = ids.view(-1).tolist(), self.model.config.image_token_index
+        P = reusable_prefix(old_ids, new_ids, img, match)
+        kept_all = match and sum(1 for t in new_ids[:P] if t == img) == sum(1 for t in old_ids if t == img)
+        return P, (n_old if (P > 0 and kept_all) else 0)
 
     def generate(self, messages: List[dict], image=None, detokenize: bool = True):
         gc, dev = self.generation_config, self.model_config.device
@@ -94,9 +136,22 @@ class Generator:
                 return any(decoded.endswith(s) for s in multi)
             return False
 
-        out, self._decoder = G.generate(self.model, ids, gc.max_new_tokens, pixel_values=pv, pixel_mask=pm, temperature=gc.temperature,
+        P, resident = 0, self._resident
+        self._resident = None   # (a call that raises leaves the cache in an unknown state)
+        reuse = getattr(gc, "reuse_prefix", False)
+        run_pv, run_pm = pv, pm
+        if reuse and resident is not None:
+            P, n_old = self._cached_prefix(resident, ids, pv, pm)
+            if P > 0 and n_old > 0:   # the old images' placeholders all lie in the prefix: the ViT sees the further images only
+                run_pv = pv[n_old:] if pv.shape[0] > n_old else None
+                run_pm = pm[n_old:] if (pm is not None and run_pv is not None) else None
+        self.last_prefill_tokens = ids.shape[1] - P
+        out, self._decoder = G.generate(self.model, ids, gc.max_new_tokens, pixel_values=run_pv, pixel_mask=run_pm, temperature=gc.temperature,
                                         top_k=gc.top_k, decoder=self._decoder, stop_token=single[0] if single else None,
-                                        callback=early_stop if (multi or len(single) > 1) else None, cache_size=gc.cache_size)
+                                        callback=early_stop if (multi or len(single) > 1) else None, cache_size=gc.cache_size,
+                                        prefill_chunk=getattr(gc, "prefill_chunk", None), cached_prefix=P)
+        if reuse:
+            self._resident = (out[:-1].tolist(), pv, pm)
         new = out[ids.shape[1]:]  # the reference returns the generated part only (generate.py:174)
         return tok.decode(new.tolist()) if detokenize else new
 
@@ -107,7 +162,9 @@ class ChatMessage:
 
 
 class AriaChat:
-    """chat.py:15-66: running history, every turn re-sends the whole conversation (images included)."""
+    """chat.py:15-66: running history; every turn hands the whole conversation (images included) to the generator.  With
+    ``GenerationConfig(reuse_prefix=True)`` the generator prefills only what the turn adds behind the cached common prefix, and images
+    whose placeholders lie in that prefix skip the ViT; without it every turn re-computes everything, as the reference does."""
 
     def __init__(self, model_config: ModelConfig, generation_config: GenerationConfig, generator: Optional[Generator] = None):
         self.generator = generator or Generator(model_config, generation_config)

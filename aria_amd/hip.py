@@ -91,6 +91,7 @@ SIGNATURES = {
     "aria_add_bf16": [P, P, P, I64, P],
     "aria_scale_bf16": [P, P, I64, P],
     "aria_attn_fwd": [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, F32, I32, P],
+    "aria_attn_fwd_offset": [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, F32, P],
     "aria_attn_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, F32, I32, P],
     "aria_attn_bwd_rope": [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, F32, I32, P, P, I64, P],
     "aria_layernorm_fwd": [P, P, P, P, P, P, I64, I64, F32, P],

@@ -953,9 +953,11 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------- attention
 def attention_fwd(q, k, v, B: int, S: int, H: int, hd: int, scale: float, causal: bool,
                   kv_len: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                  key_mask: Optional[torch.Tensor] = None, Skv: Optional[int] = None):
+                  key_mask: Optional[torch.Tensor] = None, Skv: Optional[int] = None, q_offset: Optional[int] = None):
     """q: [B*S, >= H*hd], k,v: [B*Skv, >= H*hd] token-major views (head h at columns h*hd);
-    key_mask uint8 [B, Skv] (1 = attend).  -> (o [B*S, H*hd], lse fp32 [B,H,S])."""
+    key_mask uint8 [B, Skv] (1 = attend).  -> (o [B*S, H*hd], lse fp32 [B,H,S]).
+    ``q_offset`` (an int, causal only): the S queries sit at positions q_offset.. and k / v are a KV cache of Skv rows per batch entry read
+    in place (aria_attn_fwd_offset: prefill at a cache offset); None: the plain launch."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _chk(t, name=n)
     Skv = S if Skv is None else Skv
@@ -965,6 +967,13 @@ def attention_fwd(q, k, v, B: int, S: int, H: int, hd: int, scale: float, causal
     if out is None:
         out = torch.empty((B * S, H * hd), dtype=bf16, device=q.device)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    if q_offset is not None:
+        if not causal:
+            raise ValueError("attention_fwd: q_offset needs causal=True")
+        hip.get_lib().call("aria_attn_fwd_offset", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(kv_len), _p(key_mask), B, S, Skv, int(q_offset),
+                           H, hd, _rowmajor_2d(q, "q"), _rowmajor_2d(k, "k"), _rowmajor_2d(v, "v"), _rowmajor_2d(out, "o"), float(scale),
+                           _stream(q))
+        return out, lse
     hip.get_lib().call("aria_attn_fwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(kv_len), _p(key_mask), B, S, Skv, H, hd,
                        _rowmajor_2d(q, "q"), _rowmajor_2d(k, "k"), _rowmajor_2d(v, "v"), _rowmajor_2d(out, "o"), float(scale),
                        int(causal), _stream(q))

@@ -324,6 +324,16 @@ int aria_scale_bf16(void* x, const float* scale, int64_t n, void* stream);
 int aria_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* kv_len, const uint8_t* key_mask,
                   int64_t B, int64_t Sq, int64_t Skv, int64_t H, int64_t hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
                   float scale, int causal, void* stream);
+/* Causal forward of Sq NEW queries against a KV cache read in place -- prefill at a cache offset (chunked prefill, chat prefix reuse): what
+ * the reference gets from KVCache.update indexing the cache by input_pos and the mask row causal_mask[None, None, input_pos] over the whole
+ * cache (gptfast/model.py:199-231, 76-91).  Query row i sits at position q_off + i and sees key j iff j <= q_off + i and j < klen, klen =
+ * min(Skv, q_off + Sq), further limited by kv_len[b] when given.  k, v: [B, Skv, H, hd] with rows 0..q_off+Sq-1 live; rows at or behind
+ * klen must be finite and contribute exactly nothing.  Always causal; lse (fp32 [B,H,Sq]) may be NULL.  q_off < 0 or q_off + Sq > Skv:
+ * ARIA_ERR_INVALID.  hd in {64, 128} (72, the ViT, is never causal: ARIA_ERR_UNSUPPORTED).  Alignment as aria_attn_fwd.  q_off == 0 with
+ * Sq == Skv is bit-identical to aria_attn_fwd(causal = 1). */
+int aria_attn_fwd_offset(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* kv_len, const uint8_t* key_mask,
+                         int64_t B, int64_t Sq, int64_t Skv, int64_t q_off, int64_t H, int64_t hd, int64_t ldq, int64_t ldk, int64_t ldv,
+                         int64_t ldo, float scale, void* stream);
 int aria_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
                   float* delta /* fp32 [B,H,Sq] scratch */, void* dq, void* dk, void* dv, const int32_t* kv_len,
                   const uint8_t* key_mask, int64_t B, int64_t Sq, int64_t Skv, int64_t H, int64_t hd, int64_t ldq, int64_t ldk,
@@ -341,7 +351,7 @@ int aria_attn_bwd_rope(const void* q, const void* k, const void* v, const void* 
 
 /* which backward the calling thread's last aria_attn_bwd ran: 2 = padded-tile pair (hd 64 / 72), 5 = role-split dK/dV + dQ v5 (hd 128) */
 int aria_last_attn_bwd_variant(void);
-/* which forward the calling thread's last aria_attn_fwd launched: 3 = attn_fwd3 (hd 128 / 72: software-pipelined score tiles, K / V by
+/* which forward the calling thread's last aria_attn_fwd / aria_attn_fwd_offset launched: 3 = attn_fwd3 (hd 128 / 72: software-pipelined score tiles, K / V by
  * LDS-DMA), 2 = attn_fwd2 (hd 64; or ARIA_ATTN_FWD=2: the round-3 kernels for A/B runs and the bit-identity tests) */
 int aria_last_attn_fwd_variant(void);
 
