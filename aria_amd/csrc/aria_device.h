@@ -122,6 +122,8 @@ __device__ __forceinline__ int first_lane(int v) { return emu::shfl(v, __builtin
 __device__ __forceinline__ void setprio(int) {}
 template <class T>
 __device__ __forceinline__ T atomic_add(T* p, T v) { T o = *p; *p = o + v; return o; }
+template <class T>
+__device__ __forceinline__ T atomic_or(T* p, T v) { T o = *p; *p = o | v; return o; }
 #else
 __device__ __forceinline__ void sync() { __syncthreads(); }
 template <class T>
@@ -202,6 +204,8 @@ __device__ __forceinline__ int first_lane(int v) { return __builtin_amdgcn_readf
 __device__ __forceinline__ void setprio(int) {}
 template <class T>
 __device__ __forceinline__ T atomic_add(T* p, T v) { return atomicAdd(p, v); }
+template <class T>
+__device__ __forceinline__ T atomic_or(T* p, T v) { return atomicOr(p, v); }
 #endif
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -11,6 +11,7 @@ the cursor from device memory, so it can be captured in a HIP graph (``torch.cud
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -560,17 +561,47 @@ def multinomial_sample_one_no_sync(probs_sort):
     return torch.argmax(probs_sort / q, dim=-1, keepdim=True).to(dtype=torch.int)
 
 
-def logits_to_probs(logits, temperature: float = 1.0, top_k: Optional[int] = None):
+def logits_to_probs(logits, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                    min_p: Optional[float] = None):
+    """``top_p`` / ``min_p`` (both ``None``: the reference's function, unchanged) follow aria_sample's definitions (include/aria_hip.h): over the
+    top-k survivors a distinct logit value stays iff the probability mass strictly above it is < top_p (equal logits stay or go together);
+    a logit stays iff its probability is >= min_p times the largest one."""
     logits = logits.float() / max(temperature, 1e-5)
     if top_k is not None:
         v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
         logits = torch.where(logits < v.select(-1, -1).unsqueeze(-1), -float("Inf"), logits)
+    if top_p is not None and top_p < 1.0:
+        srt, order = torch.sort(logits, dim=-1, descending=True)
+        ps = torch.softmax(srt, dim=-1)
+        excl = ps.cumsum(-1) - ps
+        new = torch.ones_like(srt, dtype=torch.bool)
+        new[..., 1:] = srt[..., 1:] != srt[..., :-1]
+        pos = torch.arange(srt.size(-1), device=srt.device).expand_as(srt)
+        first = torch.where(new, pos, torch.zeros_like(pos)).cummax(-1).values     # where this value's group of equal logits begins
+        drop = torch.zeros_like(new).scatter(-1, order, excl.gather(-1, first) >= top_p)
+        logits = logits.masked_fill(drop, -float("Inf"))
+    if min_p is not None and min_p > 0.0:
+        mx = logits.max(dim=-1, keepdim=True).values
+        logits = logits.masked_fill(logits - mx < math.log(min_p), -float("Inf"))
     return torch.softmax(logits, dim=-1)
 
 
-def sample(logits, temperature: float = 1.0, top_k: Optional[int] = None):
-    probs = logits_to_probs(logits[0, -1], temperature, top_k)
+def sample(logits, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None):
+    probs = logits_to_probs(logits[0, -1], temperature, top_k, top_p, min_p)
     return multinomial_sample_one_no_sync(probs), probs
+
+
+def sampling_options(top_p=None, min_p=None, repetition_penalty=None, logprobs=False):
+    """-> (top_p, min_p, repetition_penalty, logprobs) with ``None`` replaced by the neutral value, validated"""
+    top_p = 1.0 if top_p is None else min(float(top_p), 1.0)
+    min_p = 0.0 if min_p is None else float(min_p)
+    pen = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    if not top_p > 0.0 or not 0.0 <= min_p < 1.0 or not pen > 0.0:
+        raise ValueError(f"sampling options: need 0 < top_p, 0 <= min_p < 1, repetition_penalty > 0; got {top_p}, {min_p}, {pen}")
+    return top_p, min_p, pen, bool(logprobs)
+
+
+NEUTRAL_OPTIONS = (1.0, 0.0, 1.0, False)
 
 
 class DecodeGraph:
@@ -579,8 +610,16 @@ class DecodeGraph:
     torch kernels using the RNG) runs eagerly after the replay: capturing torch's RNG kernels in the same graph as the HIP
     launches faulted on the second replay on ROCm 7.2 / torch 2.10 (bisected in tools/bisect/debug_graph4.py)."""
 
-    def __init__(self, model: Aria, temperature: float, top_k: Optional[int], use_graph: bool = True):
+    def __init__(self, model: Aria, temperature: float, top_k: Optional[int], use_graph: bool = True, top_p: Optional[float] = None,
+                 min_p: Optional[float] = None, repetition_penalty: Optional[float] = None, logprobs: bool = False):
+        """``top_p`` / ``min_p`` / ``repetition_penalty`` / ``logprobs`` all neutral (the default): sampling is ``ops.sample_topk``, as before.
+        Otherwise every token goes through ``ops.sample`` (aria_sample): the decoder then owns ``seen`` (one bit per vocabulary entry, the tokens
+        the penalty applies to: ``begin`` fills it from a prompt, every sampled token adds its own bit) and a float32 buffer with the
+        log-probability of every token sampled since ``begin`` (``logprobs``)."""
         self.model, self.temperature, self.top_k = model, temperature, top_k
+        self.options = sampling_options(top_p, min_p, repetition_penalty, logprobs)
+        self.top_p, self.min_p, self.repetition_penalty, _ = self.options
+        self.full = self.options != NEUTRAL_OPTIONS
         dev = model.llm.output.weight.device
         self.tok = torch.zeros((1, 1), dtype=torch.long, device=dev)
         # warm-up / capture run at the LAST cache slot so they never clobber live K/V rows
@@ -590,6 +629,11 @@ class DecodeGraph:
         self._q = torch.empty(model.config.vocab_size, dtype=torch.float32, device=dev)
         self._ring = torch.zeros(model.llm.max_seq_length + 8, dtype=torch.int32, device=dev)  # one slot per new token: callers keep views
         self._slot = 0
+        self.seen = self._lp = None
+        self._n = 0
+        if self.full:
+            self.seen = torch.zeros((model.config.vocab_size + 31) // 32, dtype=torch.int32, device=dev)
+            self._lp = torch.zeros(model.llm.max_seq_length + 8, dtype=torch.float32, device=dev)
         self.graph = None
         if use_graph and dev.type == "cuda":
             s = torch.cuda.Stream()
@@ -605,6 +649,31 @@ class DecodeGraph:
     def _step(self):
         self.logits.copy_(self.model(self.tok, self.pos, last_only=True))
 
+    @property
+    def logprobs(self) -> Optional[torch.Tensor]:
+        """float32 [n]: the log-probability (under the filtered distribution it was drawn from) of every token sampled since ``begin``"""
+        return None if self._lp is None else self._lp[:min(self._n, self._lp.numel())]
+
+    def begin(self, input_ids: torch.Tensor):
+        """A new sequence: ``seen`` holds exactly the tokens of ``input_ids``, the log-prob buffer starts over."""
+        self._n = 0
+        if self.full and self.repetition_penalty != 1.0:
+            self.seen.zero_()
+            ops.token_bitmap(input_ids, self.model.config.vocab_size, out=self.seen)
+
+    def sample(self, lg: torch.Tensor) -> torch.Tensor:
+        """one token from the logits [V] (bf16, contiguous) with this decoder's options -> int32 [1] (a slot of the ring)"""
+        self._q.exponential_(1)
+        out = self._ring[self._slot:self._slot + 1]
+        self._slot = (self._slot + 1) % self._ring.numel()
+        if not self.full:
+            return ops.sample_topk(lg, self._q, self.temperature, self.top_k, out=out)
+        i = self._n % self._lp.numel()
+        self._n += 1
+        pen = self.repetition_penalty != 1.0
+        return ops.sample(lg, self._q, self.temperature, self.top_k, self.top_p, self.min_p, self.repetition_penalty,
+                          seen=self.seen if pen else None, update_seen=pen, out=out, logprob=self._lp[i:i + 1])
+
     def __call__(self, token: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
         self.tok.copy_(token.view(1, 1))
         self.pos.copy_(pos.view(1))
@@ -615,11 +684,10 @@ class DecodeGraph:
             lg = self.model(self.tok, self.pos, last_only=True)
         lg = lg.reshape(-1)
         if lg.dtype != bf16 or not lg.is_contiguous():
+            if self.full:
+                raise TypeError("DecodeGraph: top_p / min_p / repetition_penalty / logprobs need the model's bf16 logits (aria_sample)")
             return sample(lg.view(1, 1, -1), self.temperature, self.top_k)[0].view(-1)
-        self._q.exponential_(1)
-        out = self._ring[self._slot:self._slot + 1]
-        self._slot = (self._slot + 1) % self._ring.numel()
-        return ops.sample_topk(lg, self._q, self.temperature, self.top_k, out=out)
+        return self.sample(lg)
 
 
 import os as _os
@@ -638,14 +706,22 @@ def generate(model: Aria, input_ids: torch.Tensor, max_new_tokens: int, *, pixel
              temperature: float = 0.8, top_k: Optional[int] = 200, decoder: Optional[DecodeGraph] = None,
              stop_token: Optional[int] = None, use_graph: bool = False, callback=None,
              cache_size: Optional[int] = None, prefill_chunk: Optional[int] = None,
-             cached_prefix: int = 0) -> Tuple[torch.Tensor, Optional[DecodeGraph]]:
+             cached_prefix: int = 0, top_p: Optional[float] = None, min_p: Optional[float] = None,
+             repetition_penalty: Optional[float] = None, logprobs: bool = False) -> Tuple[torch.Tensor, Optional[DecodeGraph]]:
     """gptfast/generate.py:112-177: prefill (ViT + projector + full prompt) then token-by-token decode.  ``callback(new_tokens)`` is the
     reference's early-stop hook (decode_n_tokens :80-105: called after every token with the list of new token tensors, ``True`` stops);
     ``stop_token`` is the cheap form of the same for single-token stop strings.  ``cache_size`` pre-sizes the static KV cache (:139-150).
     ``cached_prefix`` = P: rows 0..P-1 of the KV cache already hold ``input_ids[:, :P]`` (an earlier call on this model left them there), so
     only the suffix is embedded and prefilled -- ``pixel_values`` / ``pixel_mask`` are then the images whose placeholders lie in the suffix.
     ``prefill_chunk``: the tokens to prefill run in pieces of at most that many (peak activation memory follows the piece, not the prompt);
-    every piece behind the first is a prefill at a cache offset (Transformer.forward with input_pos = p0 + arange)."""
+    every piece behind the first is a prefill at a cache offset (Transformer.forward with input_pos = p0 + arange).
+    ``top_p`` / ``min_p`` / ``repetition_penalty`` (HF's meanings, aria_sample's definitions in include/aria_hip.h) and ``logprobs``: with any
+    of them set every token, the first one included, is drawn by ``ops.sample``; the penalty covers all of ``input_ids`` (a cached prefix
+    too) and what the call generates; ``decoder.logprobs`` then holds the log-probabilities of the call's new tokens (float32 [n_new]).  A
+    ``decoder`` built for other values of these four is replaced.  All four neutral: the sampling of earlier releases, launch for launch."""
+    opts = sampling_options(top_p, min_p, repetition_penalty, logprobs)
+    if decoder is not None and decoder.options != opts:
+        decoder = None
     T = input_ids.size(1)
     dev = input_ids.device
     P = int(cached_prefix)
@@ -673,14 +749,23 @@ def generate(model: Aria, input_ids: torch.Tensor, max_new_tokens: int, *, pixel
             e = min(T, s + chunk)
             logits = model(None, torch.arange(s, e, device=dev), emb[:, s - P:e - P], last_only=True)
     _dbg("prefill")
-    nxt, _ = sample(logits, temperature, top_k)
-    _dbg("sample")
+    if opts == NEUTRAL_OPTIONS:
+        nxt, _ = sample(logits, temperature, top_k)
+        _dbg("sample")
     if decoder is None:
         # KNOWN ISSUE (round 1): a HIP-graph-captured decode step replays correctly inside one generate() call but faults
         # when replayed after a second image prefill (ROCm 7.2 / torch 2.10; bisection scripts tools/bisect/debug_graph*.py).
         # Decode therefore runs eagerly unless use_graph is requested explicitly.
-        decoder = DecodeGraph(model, temperature, top_k, use_graph=use_graph)
+        decoder = DecodeGraph(model, temperature, top_k, use_graph=use_graph, top_p=opts[0], min_p=opts[1], repetition_penalty=opts[2],
+                              logprobs=opts[3])
         _dbg("capture")
+    if decoder.full:   # the first token through the same launch as the others: penalty and log-prob cover it too
+        decoder.begin(input_ids)
+        lg = logits[0, -1]
+        if lg.dtype != bf16:
+            raise TypeError("generate: top_p / min_p / repetition_penalty / logprobs need the model's bf16 logits (aria_sample)")
+        nxt = decoder.sample(lg.contiguous())
+        _dbg("sample")
     toks: List[torch.Tensor] = [nxt.view(1)]
     pos = torch.tensor([T], device=dev, dtype=torch.int32)
     for _ in range(max_new_tokens - 1):

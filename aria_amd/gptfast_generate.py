@@ -17,12 +17,16 @@ from . import gptfast as G
 class GenerationConfig:
     def __init__(self, max_new_tokens: int = 100, top_k: int = 200, temperature: float = 0.8, cache_size: Optional[int] = None,
                  linear_causal_mask: bool = False, stop_strings: Optional[List[str]] = None, prefill_chunk: Optional[int] = None,
-                 reuse_prefix: bool = False):
-        """``prefill_chunk``: prefill the prompt in pieces of at most that many tokens.  ``reuse_prefix``: a ``Generator`` keeps what its last
+                 reuse_prefix: bool = False, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                 repetition_penalty: Optional[float] = None, logprobs: bool = False):
+        """``top_p`` / ``min_p`` / ``repetition_penalty``: HF's meanings (``None`` = off; ``aria_amd.gptfast.generate``); ``logprobs``: keep the
+        log-probabilities of the generated tokens (``Generator.last_logprobs``; they are also kept whenever one of the three is set).
+        ``prefill_chunk``: prefill the prompt in pieces of at most that many tokens.  ``reuse_prefix``: a ``Generator`` keeps what its last
         call left in the KV cache and prefills only what the next prompt adds behind the common prefix (multi-turn chat)."""
         self.max_new_tokens, self.top_k, self.temperature = max_new_tokens, top_k, temperature
         self.cache_size, self.linear_causal_mask, self.stop_strings = cache_size, linear_causal_mask, stop_strings
         self.prefill_chunk, self.reuse_prefix = prefill_chunk, reuse_prefix
+        self.top_p, self.min_p, self.repetition_penalty, self.logprobs = top_p, min_p, repetition_penalty, logprobs
 
 
 class ModelConfig:
@@ -80,7 +84,9 @@ class Generator:
     """generate.py:281-346.  ``Generator(model_config, generation_config).generate(messages, image, detokenize=True)``.
     With ``generation_config.reuse_prefix`` it remembers the token ids resident in the KV cache after a call (the prompt and every generated
     token that was fed back, i.e. all but the last sampled one) and that call's pixel values / masks; the next call prefills only the
-    tokens behind ``reusable_prefix``.  ``last_prefill_tokens``: how many prompt tokens the last call prefilled."""
+    tokens behind ``reusable_prefix``.  ``last_prefill_tokens``: how many prompt tokens the last call prefilled.  ``last_logprobs``: the
+    log-probabilities of the last call's new tokens (float32 [n_new]) when the configuration sets ``top_p`` / ``min_p`` /
+    ``repetition_penalty`` / ``logprobs``, else ``None``."""
 
     def __init__(self, model_config: ModelConfig, generation_config: GenerationConfig, model: Optional[G.Aria] = None, processor=None):
         self.model_config, self.generation_config = model_config, generation_config
@@ -88,6 +94,7 @@ class Generator:
         self._decoder = None
         self._resident = None            # (ids, pixel_values, pixel_mask) of what the KV cache holds (reuse_prefix)
         self.last_prefill_tokens = 0
+        self.last_logprobs = None
         if self.model is None:
             self.model, self.processor = load_model_and_processor(model_config.checkpoint_path, model_config.device, model_config.precision,
                                                                   getattr(model_config, "model_args", None), processor=processor,
@@ -149,7 +156,10 @@ class Generator:
         out, self._decoder = G.generate(self.model, ids, gc.max_new_tokens, pixel_values=run_pv, pixel_mask=run_pm, temperature=gc.temperature,
                                         top_k=gc.top_k, decoder=self._decoder, stop_token=single[0] if single else None,
                                         callback=early_stop if (multi or len(single) > 1) else None, cache_size=gc.cache_size,
-                                        prefill_chunk=getattr(gc, "prefill_chunk", None), cached_prefix=P)
+                                        prefill_chunk=getattr(gc, "prefill_chunk", None), cached_prefix=P, top_p=getattr(gc, "top_p", None),
+                                        min_p=getattr(gc, "min_p", None), repetition_penalty=getattr(gc, "repetition_penalty", None),
+                                        logprobs=getattr(gc, "logprobs", False))
+        self.last_logprobs = self._decoder.logprobs.clone() if self._decoder.full else None
         if reuse:
             self._resident = (out[:-1].tolist(), pv, pm)
         new = out[ids.shape[1]:]  # the reference returns the generated part only (generate.py:174)

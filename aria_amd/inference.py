@@ -19,6 +19,9 @@ def parse_arguments(argv=None):
     parser.add_argument("--split_image", action="store_true", default=False)
     parser.add_argument("--max_new_tokens", type=int, default=500)
     parser.add_argument("--temperature", type=float, default=0.9)
+    parser.add_argument("--top_p", type=float, default=None, help="nucleus sampling (off by default)")
+    parser.add_argument("--min_p", type=float, default=None, help="drop tokens below min_p times the top probability (off by default)")
+    parser.add_argument("--repetition_penalty", type=float, default=None, help="HF's repetition penalty over prompt and reply (off by default)")
     return parser.parse_args(argv)
 
 
@@ -44,13 +47,13 @@ def prepare_input(image_path: str, prompt: str, processor, max_image_size: int, 
 
 
 def inference(image_path: str, prompt: str, model, processor, max_image_size: int = 980, split_image: bool = False, max_new_tokens: int = 500,
-              temperature: float = 0.9) -> str:
+              temperature: float = 0.9, top_p: float = None, min_p: float = None, repetition_penalty: float = None) -> str:
     """aria/inference.py:101-131, call for call (the README quick start's generate arguments)."""
     inputs = prepare_input(image_path, prompt, processor, max_image_size, split_image)
     inputs["pixel_values"] = inputs["pixel_values"].to(model.dtype)
     inputs = {k: v.to(model.device) for k, v in inputs.items()}
     output = model.generate(**inputs, max_new_tokens=max_new_tokens, stop_strings=["<|im_end|>"], tokenizer=processor.tokenizer, do_sample=True,
-                            temperature=temperature)
+                            temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty)
     prompt_len = inputs["input_ids"].shape[1]
     return processor.tokenizer.decode(output[0][prompt_len:].tolist(), skip_special_tokens=True).replace("<|im_end|>", "")
 
@@ -61,7 +64,8 @@ def main(argv=None):
 
     processor = AriaProcessor.from_pretrained(args.base_model_path, tokenizer_path=args.tokenizer_path)   # aria/inference.py:137-139
     model = load_model(args.base_model_path, args.peft_model_path)
-    print(inference(args.image_path, args.prompt, model, processor, args.max_image_size, args.split_image, args.max_new_tokens, args.temperature))
+    print(inference(args.image_path, args.prompt, model, processor, args.max_image_size, args.split_image, args.max_new_tokens, args.temperature,
+                    args.top_p, args.min_p, args.repetition_penalty))
 
 
 if __name__ == "__main__":

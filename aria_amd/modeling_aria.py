@@ -241,13 +241,16 @@ class AriaForConditionalGeneration(nn.Module):
     def generate(self, input_ids: torch.Tensor = None, pixel_values: Optional[torch.Tensor] = None, pixel_mask: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, max_new_tokens: int = 128, do_sample: bool = True, temperature: float = 0.8,
                  top_k: Optional[int] = 200, stop_strings=None, tokenizer=None, stop_token: Optional[int] = None, refresh: bool = False,
+                 top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  **unused) -> torch.Tensor:
         """The README quick start's call (README.md:45-88: ``model.generate(**inputs, max_new_tokens=..., stop_strings=["<|im_end|>"],
         tokenizer=processor.tokenizer, do_sample=True, temperature=0.9)``) for batch 1, served by the sampling loop of
         gptfast/generate.py:112-177 on the gptfast twin (built on first use; ``refresh=True`` rebuilds it after the weights changed).
         input_ids [1, T] -> [1, T + new] like HF (prompt included).  ``do_sample=False`` is greedy; a stop string that is a single token of
         ``tokenizer`` is compared on the device, longer ones through the reference's decode-and-compare hook; ``attention_mask`` of a single
-        unpadded sequence carries no information and is ignored."""
+        unpadded sequence carries no information and is ignored.  ``top_p`` / ``min_p`` / ``repetition_penalty`` are HF's keywords with
+        HF's meanings (``None`` = off), served by the one-launch sampler (aria_sample; its tie rule and the bf16 rounding of penalised logits
+        are stated in include/aria_hip.h); with ``do_sample=False`` the penalty still applies, as in HF."""
         from . import gptfast as G
 
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
@@ -258,7 +261,7 @@ class AriaForConditionalGeneration(nn.Module):
             object.__setattr__(self, "_gptfast_twin", self.to_gptfast())
             object.__setattr__(self, "_gptfast_decoder", None)
         if not do_sample:
-            temperature, top_k = 1.0, 1
+            temperature, top_k, top_p, min_p = 1.0, 1, None, None
         callback = None
         if stop_strings:
             if tokenizer is None:
@@ -274,12 +277,13 @@ class AriaForConditionalGeneration(nn.Module):
                 def callback(tokens):
                     decoded = tokenizer.decode(torch.cat(tokens).tolist())
                     return any(decoded.endswith(t) for t in multi)
-        key = (float(temperature), top_k)
+        key = (float(temperature), top_k) + G.sampling_options(top_p, min_p, repetition_penalty)
         if getattr(self, "_gptfast_sampling", key) != key:  # the cached decoder closes over its sampling parameters
             object.__setattr__(self, "_gptfast_decoder", None)
         object.__setattr__(self, "_gptfast_sampling", key)
         out, dec = G.generate(self._gptfast_twin, input_ids, max_new_tokens, pixel_values=pixel_values, pixel_mask=pixel_mask,
-                              temperature=temperature, top_k=top_k, decoder=self._gptfast_decoder, stop_token=stop_token, callback=callback)
+                              temperature=temperature, top_k=top_k, decoder=self._gptfast_decoder, stop_token=stop_token, callback=callback,
+                              top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty)
         object.__setattr__(self, "_gptfast_decoder", dec)
         return out.view(1, -1)
 

@@ -486,6 +486,44 @@ def sample_topk(logits: torch.Tensor, q: torch.Tensor, temperature: float, top_k
     return out
 
 
+def sample(logits: torch.Tensor, q: torch.Tensor, temperature: float, top_k: Optional[int], top_p: float = 1.0, min_p: float = 0.0,
+           repetition_penalty: float = 1.0, seen: Optional[torch.Tensor] = None, update_seen: bool = False, out: Optional[torch.Tensor] = None,
+           logprob: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None):
+    """The full sampler for one token in one launch (aria_sample): repetition penalty on the tokens whose bit is set in ``seen`` (int32
+    bitmap, ``token_bitmap``), temperature, top-k, top-p, min-p in HF's order, then argmax p / q on the caller's Exp(1) draws -> int32 [1].
+    ``logprob`` (float32 [1]) receives the log-probability of the returned token under the filtered distribution, ``kept`` (int32 [1]) the
+    size of the kept set; ``update_seen`` sets the returned token's bit in ``seen``."""
+    _chk(logits, name="logits"), _chk(q, torch.float32, "q")
+    assert logits.is_contiguous() and q.is_contiguous() and logits.numel() == q.numel()
+    V = logits.numel()
+    if seen is not None:
+        _chk(seen, torch.int32, "seen")
+        if not seen.is_contiguous() or seen.numel() < (V + 31) // 32:
+            raise ValueError(f"sample: seen needs {(V + 31) // 32} contiguous int32 words, got {seen.numel()}")
+    if logprob is not None:
+        _chk(logprob, torch.float32, "logprob")
+    if kept is not None:
+        _chk(kept, torch.int32, "kept")
+    if out is None:
+        out = torch.empty(1, dtype=torch.int32, device=logits.device)
+    hip.get_lib().call("aria_sample", _p(logits), _p(q), V, int(top_k or 0), float(temperature), float(top_p), float(min_p),
+                       float(repetition_penalty), _p(seen), int(bool(update_seen)), _p(out), _p(logprob), _p(kept), _stream(logits))
+    return out
+
+
+def token_bitmap(ids: torch.Tensor, V: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One bit per vocabulary entry, set for every id in ``ids`` (any shape, integer; ids outside [0, V) are ignored) -> int32
+    [ceil(V / 32)] (aria_token_bitmap).  ``out``: an existing bitmap to add the bits to (zero it first for a fresh one)."""
+    if out is None:
+        out = torch.zeros((V + 31) // 32, dtype=torch.int32, device=ids.device)
+    _chk(out, torch.int32, "out")
+    if not out.is_contiguous() or out.numel() < (V + 31) // 32:
+        raise ValueError(f"token_bitmap: out needs {(V + 31) // 32} contiguous int32 words")
+    ids32 = ids.reshape(-1).to(torch.int32).contiguous()
+    hip.get_lib().call("aria_token_bitmap", _p(ids32) if ids32.numel() else None, ids32.numel(), int(V), _p(out), _stream(out))
+    return out
+
+
 def dequant_w8(q: torch.Tensor, scales: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Int8 weight-only codes -> bf16 (aria_dequant_w8_bf16): q int8 [..., C] with one bf16 scale per row (scales [...]) ->
     out[r, c] = bf16(float(q[r, c]) * float(s[r])), the same bits as ``(q.float() * s.float()[..., None]).to(bfloat16)``."""

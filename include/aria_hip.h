@@ -425,6 +425,31 @@ int aria_decode_trace_layout(const int64_t* dims, int64_t* out);
  * all), p_i ~ exp((l_i - max) / max(temperature, 1e-5)), out[0] = argmax_i p_i / q_i with q [V] fp32 the caller's Exp(1) draws
  * (multinomial_sample_one_no_sync's trick: the caller's generator stays the source of randomness).  logits bf16 [V]. */
 int aria_sample_topk(const void* logits, const float* q, int64_t V, int64_t top_k, float temperature, int32_t* out, void* stream);
+/* The full sampler as ONE launch (sample.hip): the steps of HF's processor chain, in its order, on one token's logits (bf16 [V]).
+ *  1. repetition penalty: every token i whose bit is set in `seen` (bit i & 31 of word i >> 5; ceil(V / 32) words) gets
+ *     l_i <- bf16_rne(l_i < 0 ? l_i * pen : l_i / pen), computed in fp32.  Rounding the result back to bf16 is THIS library's definition
+ *     (HF's RepetitionPenaltyLogitsProcessor keeps fp32): every logit keeps a 16-bit order key, so the radix select below stays exact.
+ *     pen == 1 or seen == NULL: no penalty.  The maximum and every later step see the penalised logits.
+ *  2. temperature and top-k exactly as aria_sample_topk: T = max(temperature, 1e-5); the logits >= the top_k-th largest are kept, ties at
+ *     that value included; top_k <= 0 or >= V keeps all.
+ *  3. top-p over the top-k survivors, p = their softmax: a distinct logit value v is kept iff the probability mass of the logits strictly
+ *     greater than v is < top_p.  Equal logits are kept or dropped together, the maximum is always kept, top_p >= 1 keeps all.  (This is
+ *     HF's TopPLogitsWarper unless the boundary falls inside a group of equal logits: HF keeps part of the group by sort order, this
+ *     kernel all of it.)
+ *  4. min-p: i is kept iff exp((l_i - max) / T) >= min_p; min_p <= 0 keeps all.
+ * out_token[0] = argmax_i p_i / q_i over the kept set, q [V] fp32 the caller's Exp(1) draws, the lowest index winning exact ties;
+ * out_kept[0] (or NULL) = the size of the kept set -- every filter is a threshold on the value, so the set is "the out_kept largest, ties
+ * whole"; out_logprob[0] (or NULL) = (l_c - max) / T - log(sum over the kept set of exp((l_i - max) / T)) for the returned token c.
+ * update_seen != 0 also sets the returned token's bit in `seen` (needs seen != NULL; it is set even when pen == 1).
+ * The three outputs are a pure function of the inputs (the top-p boundary is decided on integer masses, 2^40 fixed point).
+ * V <= 2^20 (ARIA_ERR_UNSUPPORTED beyond); top_p <= 0, min_p < 0, min_p >= 1, repetition_penalty <= 0 or a NaN parameter:
+ * ARIA_ERR_INVALID; logits 16-byte aligned. */
+int aria_sample(const void* logits, const float* q, int64_t V, int64_t top_k, float temperature, float top_p, float min_p,
+                float repetition_penalty, uint32_t* seen, int update_seen, int32_t* out_token, float* out_logprob, int32_t* out_kept,
+                void* stream);
+/* Sets the bits of ids [n] (int32) in the bitmap `seen` (ceil(V / 32) words, zeroed by the caller or holding earlier bits to keep).  Ids
+ * outside [0, V) are ignored, duplicates are fine.  With aria_sample's update_seen the penalty costs O(1) per generated token. */
+int aria_token_bitmap(const int32_t* ids, int64_t n, int64_t V, uint32_t* seen, void* stream);
 /* The routing step of the engine on its own (gptfast/model.py:359-363 for one token; what every workgroup of the routed up-projection
  * runs in front of its rows): top-k of E bf16 logits with ties to the lowest expert id, softmax over the selected logits in fp32,
  * scores as bf16 -- the same function as aria_moe_route on one row (bit-exact ids and scores). */

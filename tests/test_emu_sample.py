@@ -1,0 +1,90 @@
+"""The full sampler through the SIMT emulator (CPU): aria_sample / aria_token_bitmap against the float64 oracle, the oracle against
+transformers' processors, and the top_p / min_p / repetition_penalty / logprobs options of the gptfast surface (tests/sample_cases.py)."""
+import pytest
+
+from tests import sample_cases as S
+
+DEV = "cpu"
+VOCABS = [1, 7, 8, 1000, 8200, 100352]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def emu():
+    from tests.emu import emu_lib
+
+    emu_lib.install()
+    yield
+    emu_lib.uninstall()
+    print("largest log-prob error seen:", S.OBSERVED["logprob_err"])
+
+
+@pytest.mark.parametrize("sigma", [1.0, 4.0])
+@pytest.mark.parametrize("V", VOCABS)
+def test_vocabulary_sizes(V, sigma):
+    S.case_vocab(DEV, V, sigma)
+
+
+def test_peaked():
+    S.case_peaked(DEV)
+
+
+def test_all_logits_equal():
+    S.case_all_equal(DEV)
+
+
+def test_two_distinct_values():
+    S.case_two_values(DEV)
+
+
+def test_filter_interplay():
+    S.case_interplay(DEV)
+
+
+def test_penalty():
+    S.case_penalty(DEV)
+
+
+def test_update_seen():
+    S.case_update_seen(DEV)
+
+
+@pytest.mark.parametrize("V", VOCABS)
+def test_neutral_options_are_sample_topk(V):
+    S.case_neutral(DEV, V)
+
+
+def test_determinism():
+    S.case_determinism(DEV)
+
+
+def test_validation():
+    S.case_validation(DEV)
+
+
+def test_oracle_vs_transformers():
+    S.case_oracle_vs_transformers()
+
+
+def test_tensor_path():
+    S.case_tensor_path()
+
+
+@pytest.mark.parametrize("opts", S.OPTION_SETS, ids=["top_p", "min_p"])
+def test_generate_vs_oracle(opts):
+    S.case_generate_vs_oracle(DEV, opts)
+
+
+def test_generate_options():
+    S.case_generate_options(DEV)
+
+
+def test_generator_turns():
+    S.case_generator_turns(DEV)
+
+
+def test_hf_generate(golden):
+    S.case_hf_generate(DEV, golden)
+
+
+def test_inference_flags():
+    S.case_inference_flags()
